@@ -516,6 +516,37 @@ def drive(step, reducer, steps: int, warmup: int, prewarm: int, sync, barrier, a
     return time.perf_counter() - t0, last
 
 
+DUMP_ROWS = 1024                # filterbank output rows (hops) in the dump: 1024 x 1024 complex64 = 8 MB
+
+
+def dump_outputs(out_dir: str, out, stats, merged) -> None:
+    """What the last timed step handed its caller, as float32 / float64 .npy files (about 8 MB in all):
+      pfb_rows.npy        float32 (DUMP_ROWS, 1024, 2): filterbank output rows (re, im) -- the first and last 16 hops
+                          and a fixed seeded sample of the rest (the full output is 4 GB at 2^28 samples)
+      pfb_row_index.npy   float64 (DUMP_ROWS,): the hop index of each of those rows
+      scan_stats.npy      float64 (1024, 5): this rank's per-channel statistics of the last scan window
+      scan_stats_merged.npy  float64 (1024, 5): the statistics merged over all ranks (--gpus > 1 only)
+    The input is seeded, so the same arguments give the same inputs on every run."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    hops = out.shape[0]
+    if hops <= DUMP_ROWS:
+        idx = np.arange(hops)
+    else:
+        edge = np.concatenate([np.arange(16), np.arange(hops - 16, hops)])
+        rest = np.setdiff1d(np.arange(hops), edge)
+        pick = np.random.default_rng(20240601).choice(rest, DUMP_ROWS - edge.size, replace=False)
+        idx = np.sort(np.concatenate([edge, pick]))
+    rows = out.index_select(0, torch.from_numpy(idx).to(out.device))
+    np.save(os.path.join(out_dir, "pfb_rows.npy"), torch.view_as_real(rows).cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "pfb_row_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "scan_stats.npy"), stats.cpu().numpy().astype(np.float64))
+    if merged is not None:
+        np.save(os.path.join(out_dir, "scan_stats_merged.npy"), merged.cpu().numpy().astype(np.float64))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -524,7 +555,11 @@ def main() -> None:
     ap.add_argument("--log2n", type=int, default=28, help="samples per step = 2^log2n")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the configs[1]/configs[3] side measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import torch.distributed as dist
@@ -587,6 +622,8 @@ def main() -> None:
     # load rather than on the DVFS ramp of a cold device
     elapsed, last = drive(step, reducer, args.steps, args.warmup, 200, torch.cuda.synchronize,
                           dist.barrier if world > 1 else (lambda: None))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, stats2[(it[0] - 1) & 1], last)
     # HIP events around the fused kernel of every timed step, on the stream it is launched on (the handle keeps the event
     # pairs of its last 64 launches): read AFTER the timed region, so no step waits for the host
     kernel_ms = [ch.last_kernel_ms(back=b) for b in range(min(args.steps, 64))]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Boundary facts of the drop-in, checked against the REAL reference package (build container only: needs
-/root/reference; never shipped to or run on the GPU box -- tests/test_boundary.py runs it when the reference is there).
+/root/reference; never shipped to or run on the GPU box -- tests/test_boundary.py checks the recorded facts, see --record).
 
   1. the reference's own ChannelConfig (capture.py:448-506) drives wavehip.channel_ops.build_chain for every mode the
      dispatcher serves (capture.py:340-414), and our ChannelConfig has the same fields and defaults;
@@ -10,9 +10,14 @@
   4. constructor / method signatures of the drop-in classes equal the reference's (inspect.signature):
      C4FMDemodulator, CQPSKDemodulator (Phase 2 and the LSM one), PolyphaseChannelizer, ChannelClassifier,
      P25P1SoftSyncDetector, GardnerTED; _process_channel_dsp_stateless's parameter list.
-Exit code 0 = all hold; prints one line per fact."""
+Exit code 0 = all hold; prints one line per fact.
+
+  --record   when every fact holds, also write the reference side of facts 1-5 (ChannelConfig fields and defaults, the
+             FFT base surface, the signatures) to tests/golden/boundary_facts.json, which tests/test_boundary.py checks
+             the package against without the reference."""
 import dataclasses
 import inspect
+import json
 import os
 import sys
 
@@ -35,6 +40,13 @@ def check(ok, what):
     print(("ok   " if ok else "FAIL ") + what)
     if not ok:
         fails.append(what)
+
+
+def wavehip_attr(path):
+    obj = wavehip
+    for part in path.split("."):
+        obj = getattr(obj, part)
+    return obj
 
 
 def params(f, skip_self=True):
@@ -89,27 +101,27 @@ from wavecapsdr.decoders import p25 as rp25, p25_framer as rfr  # noqa: E402
 from wavecapsdr import channel_classifier as rcc  # noqa: E402
 
 pairs = [
-    ("C4FMDemodulator.__init__", rc4.C4FMDemodulator.__init__, wavehip.C4FMDemodulator.__init__),
-    ("C4FMDemodulator.demodulate", rc4.C4FMDemodulator.demodulate, wavehip.C4FMDemodulator.demodulate),
-    ("CQPSKDemodulator (Phase 2).__init__", rcq.CQPSKDemodulator.__init__, wavehip.CQPSKDemodulator.__init__),
-    ("CQPSKDemodulator (Phase 2).demodulate", rcq.CQPSKDemodulator.demodulate, wavehip.CQPSKDemodulator.demodulate),
-    ("decoders.p25.CQPSKDemodulator (LSM).__init__", rp25.CQPSKDemodulator.__init__, wavehip.LSMDemodulator.__init__),
-    ("decoders.p25.CQPSKDemodulator (LSM).demodulate", rp25.CQPSKDemodulator.demodulate, wavehip.LSMDemodulator.demodulate),
-    ("PolyphaseChannelizer.__init__", rch.PolyphaseChannelizer.__init__, wavehip.PolyphaseChannelizer.__init__),
-    ("PolyphaseChannelizer.process", rch.PolyphaseChannelizer.process, wavehip.PolyphaseChannelizer.process),
-    ("PolyphaseChannelizer.extract_channel", rch.PolyphaseChannelizer.extract_channel, wavehip.PolyphaseChannelizer.extract_channel),
-    ("ChannelClassifier.__init__", rcc.ChannelClassifier.__init__, wavehip.ChannelClassifier.__init__),
-    ("ChannelClassifier.update", rcc.ChannelClassifier.update, wavehip.ChannelClassifier.update),
-    ("P25P1SoftSyncDetector.process_batch", rfr.P25P1SoftSyncDetector.process_batch, wavehip.P25P1SoftSyncDetector.process_batch),
-    ("GardnerTED.__init__", rst.GardnerTED.__init__, wavehip.GardnerTED.__init__),
-    ("MuellerMullerTED.__init__", rst.MuellerMullerTED.__init__, wavehip.MuellerMullerTED.__init__),
-    ("MuellerMullerTED.process_block", rst.MuellerMullerTED.process_block, wavehip.MuellerMullerTED.process_block),
-    ("CostasLoop.__init__", rcq.CostasLoop.__init__, wavehip.CostasLoop.__init__),
-    ("CostasLoop.process", rcq.CostasLoop.process, wavehip.CostasLoop.process),
-    ("CostasLoop.process_block", rcq.CostasLoop.process_block, wavehip.CostasLoop.process_block),
+    ("C4FMDemodulator.__init__", rc4.C4FMDemodulator.__init__, "C4FMDemodulator.__init__"),
+    ("C4FMDemodulator.demodulate", rc4.C4FMDemodulator.demodulate, "C4FMDemodulator.demodulate"),
+    ("CQPSKDemodulator (Phase 2).__init__", rcq.CQPSKDemodulator.__init__, "CQPSKDemodulator.__init__"),
+    ("CQPSKDemodulator (Phase 2).demodulate", rcq.CQPSKDemodulator.demodulate, "CQPSKDemodulator.demodulate"),
+    ("decoders.p25.CQPSKDemodulator (LSM).__init__", rp25.CQPSKDemodulator.__init__, "LSMDemodulator.__init__"),
+    ("decoders.p25.CQPSKDemodulator (LSM).demodulate", rp25.CQPSKDemodulator.demodulate, "LSMDemodulator.demodulate"),
+    ("PolyphaseChannelizer.__init__", rch.PolyphaseChannelizer.__init__, "PolyphaseChannelizer.__init__"),
+    ("PolyphaseChannelizer.process", rch.PolyphaseChannelizer.process, "PolyphaseChannelizer.process"),
+    ("PolyphaseChannelizer.extract_channel", rch.PolyphaseChannelizer.extract_channel, "PolyphaseChannelizer.extract_channel"),
+    ("ChannelClassifier.__init__", rcc.ChannelClassifier.__init__, "ChannelClassifier.__init__"),
+    ("ChannelClassifier.update", rcc.ChannelClassifier.update, "ChannelClassifier.update"),
+    ("P25P1SoftSyncDetector.process_batch", rfr.P25P1SoftSyncDetector.process_batch, "P25P1SoftSyncDetector.process_batch"),
+    ("GardnerTED.__init__", rst.GardnerTED.__init__, "GardnerTED.__init__"),
+    ("MuellerMullerTED.__init__", rst.MuellerMullerTED.__init__, "MuellerMullerTED.__init__"),
+    ("MuellerMullerTED.process_block", rst.MuellerMullerTED.process_block, "MuellerMullerTED.process_block"),
+    ("CostasLoop.__init__", rcq.CostasLoop.__init__, "CostasLoop.__init__"),
+    ("CostasLoop.process", rcq.CostasLoop.process, "CostasLoop.process"),
+    ("CostasLoop.process_block", rcq.CostasLoop.process_block, "CostasLoop.process_block"),
 ]
-for name, a, b in pairs:
-    pa, pb = params(a), params(b)
+for name, a, path in pairs:
+    pa, pb = params(a), params(wavehip_attr(path))
     # names, order and defaults must agree; extra keyword-only / **kwargs tails are the drop-in's own business
     n = len(pa)
     same = [(x[0], x[1]) for x in pa] == [(x[0], x[1]) for x in pb[:n]] or \
@@ -126,7 +138,8 @@ import numpy as np  # noqa: E402
 import wavehip.capture_seam as seam  # noqa: E402
 from wavecapsdr.devices.fake import FakeDriver  # noqa: E402
 
-check(params(rc.Capture._process_channels_parallel) == params(seam.process_channels_parallel)[1:],
+cap_parallel = rc.Capture._process_channels_parallel                            # (rebound below)
+check(params(cap_parallel) == params(seam.process_channels_parallel)[1:],
       "process_channels_parallel(capture, samples, executor, timeout=0.5) = the reference method's parameters after self")
 cap = rc.Capture(cfg=rc.CaptureConfig(id="c1", device_id="fake0", center_hz=1_000_000.0, sample_rate=1_000_000), driver=FakeDriver())
 ch = rc.Channel(rc.ChannelConfig(id="ch1", capture_id="c1", mode="wbfm"))
@@ -158,4 +171,32 @@ finally:
     seam.dispatch_chunk = orig
 
 print(f"{len(fails)} boundary facts failed" if fails else "all boundary facts hold")
+if "--record" in sys.argv[1:] and not fails:
+    def jparams(f, skip_self=True):
+        return [[q[0], q[1] if q[1] == "<required>" else repr(q[1]), q[2]] for q in params(f, skip_self)]
+
+    def field_default(f):
+        if f.default is not dataclasses.MISSING:
+            return {"default": f.default}
+        if f.default_factory is not dataclasses.MISSING:
+            return {"default": f.default_factory(), "factory": True}
+        return {}
+
+    facts = {
+        "about": "reference side of the boundary facts, written by oracle/check_boundary.py --record; "
+                 "defaults of signatures are repr() strings",
+        "channel_config": {f.name: field_default(f) for f in dataclasses.fields(rc.ChannelConfig)},
+        "process_channel_dsp_stateless": jparams(rc._process_channel_dsp_stateless, False),
+        "fft_result_fields": [f.name for f in dataclasses.fields(rbase.FFTResult)],
+        "fft_backend_abstract": sorted(rbase.FFTBackend.__abstractmethods__),
+        "fft_backend_init": jparams(rbase.FFTBackend.__init__),
+        "fft_backend_execute": jparams(rbase.FFTBackend.execute),
+        "signatures": [{"name": name, "wavehip": path, "reference": jparams(a)} for name, a, path in pairs],
+        "capture_process_channels_parallel": jparams(cap_parallel),
+    }
+    out = os.path.join(REPO, "tests", "golden", "boundary_facts.json")
+    with open(out, "w") as fh:
+        json.dump(facts, fh, indent=1)
+        fh.write("\n")
+    print(f"wrote {out}")
 sys.exit(1 if fails else 0)
