@@ -177,8 +177,8 @@ struct FmArgs {
     const float *nco_c; // [K] f32(-2 pi off/fs); 0 => no mix
     const double *taps; // [ntaps]
     int fmt, N, K, n_out, ntaps, down, d0, TO, R;   // R: output tiles per workgroup (fused kernel)
-    const float *araw;      // fused kernel, fast front: [n_chunks][N] raw discriminator angles (fm_rawdisc_kernel); NaN where the
-                            // sample pair's product is exactly zero; nullptr = the per-channel front of round 2
+    const float *araw;      // fused kernel's front: [n_chunks][N] raw discriminator angles (fm_rawdisc_kernel); NaN where the
+                            // sample pair's product is exactly zero
     const float2 *tphase;   // fir_phase: float2 [21][32] = the tap pairs (trev[q down + 2 rp], trev[.. + 1]) by block and phase pair
     int fir_phase;      // fused kernel: != 0 -> the decimating FIR runs in its polyphase register form (fm_fir_phases), TO = 128
     float scale;        // fs / (2 pi 75000)
@@ -252,23 +252,20 @@ __device__ __forceinline__ float fm_single_zero(const FmArgs &a, size_t in_base,
     return fast_atan2f_x2(fm_v2f{im, im}, fm_v2f{re, re}).x;
 }
 
-// Phase 1 of the fused kernel, TWO samples per lane: lane l of a wave takes the window indices s0 + 2l - 1 and s0 + 2l (a
-// wave advances 127 samples per step; lane 0's first sample only supplies x[n-1]).  The previous sample of the second one
-// is the lane's own first, that of the first one the neighbour's second (one shuffle per two samples), both samples of
-// int16 input come in with one 8-byte load, and the NCO / mix / discriminator / atan2 arithmetic of the pair goes out as
-// packed instructions.  Per sample the operations are those of the one-sample form (same results for a sample whichever
+// The unfused chains' FM front (chan_front_kernel), TWO samples per lane: lane l of a wave takes the window indices
+// s0 + 2l - 1 and s0 + 2l (a wave advances 127 samples per step; lane 0's first sample only supplies x[n-1]).  The
+// previous sample of the second one is the lane's own first, that of the first one the neighbour's second (one shuffle
+// per two samples), both samples of int16 input come in with one 8-byte load, and the NCO / mix / discriminator / atan2
+// arithmetic of the pair goes out as packed instructions.  Per sample the operations are those of the one-sample form (same results for a sample whichever
 // slot computes it): 87 -> about 65 issue slots per sample and channel.
 // Power sums (rms_normalize needs sum v^2 of the whole row, the metrics sum |base|^2): float32 PER PASS AND LANE -- a
-// lane meets at most ~30 samples in a pass -- folded into the float64 run sums once per pass.  A pass's step grid is
-// anchored at the pass's first window index, and which pass computes a sample does not depend on how the row is cut
-// into runs (see the ownership rule in the kernel), so the sums stay independent of the batch size bit for bit.
-// BASE: sum |x|^2 of the RAW samples -- |x e^(j theta)| = |x|, the reference's rssi_db is the power of the mixed but
-// unfiltered chunk (capture.py:330-334), i.e. the same number for every channel of a capture up to the rounding of
-// |e^(j theta)| (1e-7) -- so only channel 0's workgroups take it and the finalize kernel shares it.
+// lane meets at most ~30 samples in a pass -- folded into the float64 sums once per pass; samples in [own_lo, own_hi)
+// only.  BASE: sum |x|^2 of the RAW samples -- |x e^(j theta)| = |x|, the reference's rssi_db is the power of the mixed
+// but unfiltered chunk (capture.py:330-334).
 template <bool CHECK, int FMT, bool MIX>
 __device__ __forceinline__ void fm_phase1(const FmArgs &a, float *fm_s, int i_lo, int i_hi, int n_lo, int N, float c,
                                           size_t in_base, int own_lo, int own_hi, int lane, int wave,
-                                          double &p_base, double &p_fm, const bool base) {
+                                          double &p_base, double &p_fm) {
     float sb_a = 0.f, sb_b = 0.f, sf_a = 0.f, sf_b = 0.f;   // the pass's float32 sums: a-slots and b-slots apart
     // interior passes (no bounds checks) load one step ahead: the pair of the NEXT step is in flight while this one is
     // mixed and discriminated (the last step re-reads its own pair)
@@ -297,8 +294,7 @@ __device__ __forceinline__ void fm_phase1(const FmArgs &a, float *fm_s, int i_lo
             if (va) { const float2 v = load_iq(a.in, FMT, in_base + na); bx.x = v.x; by.x = v.y; }
             if (vb) { const float2 v = load_iq(a.in, FMT, in_base + nb); bx.y = v.x; by.y = v.y; }
         }
-        fm_v2f pw = {0.f, 0.f};
-        if (base) pw = __builtin_elementwise_fma(bx, bx, by * by);   // raw power (uniform branch: channel 0 only)
+        const fm_v2f pw = __builtin_elementwise_fma(bx, bx, by * by);   // raw power
         if (MIX) {   // mix_fast on the pair
             const fm_v2f C_HI = {0.15915494f, 0.15915494f}, C_LO = {6.4206382e-09f, 6.4206382e-09f};
             const fm_v2f ph = fm_v2f{c, c} * fm_v2f{(float)na, (float)nb};
@@ -499,13 +495,32 @@ __device__ __forceinline__ void fm_fir_phases(const float *fm_s, const fm_v2f (&
     if (rp < NS && o < mcnt) out[o] = outv;
 }
 
+// Front::run<CHECK, FMT, MIX>(x...) with the instance picked at run time (fmt 1: int16 input, else complex64)
+template <class Front, class... A>
+__device__ __forceinline__ void fm_dispatch(bool check, int fmt, bool mix, A &&...x) {
+    if (!check) {
+        if (fmt == 1) { if (mix) Front::template run<false, 1, true>(x...); else Front::template run<false, 1, false>(x...); }
+        else          { if (mix) Front::template run<false, 0, true>(x...); else Front::template run<false, 0, false>(x...); }
+    } else {
+        if (fmt == 1) { if (mix) Front::template run<true, 1, true>(x...); else Front::template run<true, 1, false>(x...); }
+        else          { if (mix) Front::template run<true, 0, true>(x...); else Front::template run<true, 0, false>(x...); }
+    }
+}
+
+struct FmFront {
+    template <bool C, int F, bool M, class... A> __device__ __forceinline__ static void run(A &&...x) { fm_phase1<C, F, M>(x...); }
+};
+struct FmFrontFast {
+    template <bool C, int F, bool M, class... A> __device__ __forceinline__ static void run(A &&...x) { fm_phase1_fast<C, F, M>(x...); }
+};
+
 // ROWS: the unfused chains' decimating FIR (the window is copied from a.rows_src instead of computed by phase 1)
 template <bool ROWS>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 5))) void fmbank_fused_kernel(FmArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float *taps_s = reinterpret_cast<float *>(smem_raw);                       // taps rounded to float32, reversed
     float *fm_s = reinterpret_cast<float *>(smem_raw + (size_t)((a.ntaps + 1) & ~1) * sizeof(float));
-    __shared__ double red[8];
+    __shared__ double red[4];
 
     const int run = blockIdx.x, k = blockIdx.y, chunk = blockIdx.z;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -551,7 +566,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 5))) voi
     const float c = a.nco_c[k];
     const bool do_mix = c != 0.0f;
     const size_t in_base = (size_t)chunk * N;
-    double p_base = 0.0, p_fm = 0.0;
+    double p_fm = 0.0;
 
     for (int tile = t_lo; tile < t_hi; ++tile) {
         const int m0 = tile * a.TO;
@@ -564,35 +579,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 5))) voi
         // interior: every sample this pass touches (incl. lane 0's predecessor sample and the idle lanes of its last
         // 127-sample step) exists, every sample it stores is owned and has a predecessor
         const bool interior = n_lo + i_lo >= (own_lo > 1 ? own_lo : 1) && n_lo + W <= own_hi && n_lo + W + 128 <= N;
-        const bool fast = a.araw != nullptr;           // raw angles taken once per chunk (fm_rawdisc_kernel, with sum |x|^2)
-        const bool base = k == 0 && !fast;
-#define WH_P1X(CHK, F, M, LO, HI, OL, OH, PB, PF) \
-    fm_phase1<CHK, F, M>(a, fm_s, LO, HI, n_lo, N, c, in_base, OL, OH, lane, wave, PB, PF, base)
-#define WH_P1(CHK, F, M) WH_P1X(CHK, F, M, i_lo, W, own_lo, own_hi, p_base, p_fm)
-#define WH_P1F(CHK, F, M, LO, HI, OL, OH, PF, SUMS) \
-    fm_phase1_fast<CHK, F, M>(a, fm_s, LO, HI, n_lo, N, c, in_base, OL, OH, lane, wave, PF, SUMS)
         if (head) {
-            // the carried part of the window, owned by earlier runs: computed, not summed (empty ownership range; its sums
-            // go to scratch variables)
-            double nb_ = 0.0, nf_ = 0.0;
+            // the carried part of the window, owned by earlier runs: computed, not summed
             const bool in_a = n_lo >= 1 && n_lo + keep + 128 <= N;
-#define WH_P1A(CHK, F, M) WH_P1X(CHK, F, M, 0, keep, 0, 0, nb_, nf_)
-            if (fast) {
-                if (in_a) {
-                    if (a.fmt == 1) { if (do_mix) WH_P1F(false, 1, true, 0, keep, 0, 0, nf_, false); else WH_P1F(false, 1, false, 0, keep, 0, 0, nf_, false); }
-                    else            { if (do_mix) WH_P1F(false, 0, true, 0, keep, 0, 0, nf_, false); else WH_P1F(false, 0, false, 0, keep, 0, 0, nf_, false); }
-                } else {
-                    if (a.fmt == 1) { if (do_mix) WH_P1F(true, 1, true, 0, keep, 0, 0, nf_, false); else WH_P1F(true, 1, false, 0, keep, 0, 0, nf_, false); }
-                    else            { if (do_mix) WH_P1F(true, 0, true, 0, keep, 0, 0, nf_, false); else WH_P1F(true, 0, false, 0, keep, 0, 0, nf_, false); }
-                }
-            } else if (in_a) {
-                if (a.fmt == 1) { if (do_mix) WH_P1A(false, 1, true); else WH_P1A(false, 1, false); }
-                else            { if (do_mix) WH_P1A(false, 0, true); else WH_P1A(false, 0, false); }
-            } else {
-                if (a.fmt == 1) { if (do_mix) WH_P1A(true, 1, true); else WH_P1A(true, 1, false); }
-                else            { if (do_mix) WH_P1A(true, 0, true); else WH_P1A(true, 0, false); }
-            }
-#undef WH_P1A
+            fm_dispatch<FmFrontFast>(!in_a, a.fmt, do_mix, a, fm_s, 0, keep, n_lo, N, c, in_base, 0, 0, lane, wave, p_fm, false);
         }
         if (ROWS) {
             // unfused chains (IIR stages, AGC, AM / SSB fronts): the rows are in memory already; this kernel is their
@@ -603,24 +593,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 5))) voi
                 const int n = n_lo + i;
                 fm_s[i] = (n >= 0 && n < N) ? rw[n] : 0.0f;
             }
-        } else if (fast) {
-            if (interior) {
-                if (a.fmt == 1) { if (do_mix) WH_P1F(false, 1, true, i_lo, W, own_lo, own_hi, p_fm, true); else WH_P1F(false, 1, false, i_lo, W, own_lo, own_hi, p_fm, true); }
-                else            { if (do_mix) WH_P1F(false, 0, true, i_lo, W, own_lo, own_hi, p_fm, true); else WH_P1F(false, 0, false, i_lo, W, own_lo, own_hi, p_fm, true); }
-            } else {
-                if (a.fmt == 1) { if (do_mix) WH_P1F(true, 1, true, i_lo, W, own_lo, own_hi, p_fm, true); else WH_P1F(true, 1, false, i_lo, W, own_lo, own_hi, p_fm, true); }
-                else            { if (do_mix) WH_P1F(true, 0, true, i_lo, W, own_lo, own_hi, p_fm, true); else WH_P1F(true, 0, false, i_lo, W, own_lo, own_hi, p_fm, true); }
-            }
-        } else if (interior) {
-            if (a.fmt == 1) { if (do_mix) WH_P1(false, 1, true); else WH_P1(false, 1, false); }
-            else            { if (do_mix) WH_P1(false, 0, true); else WH_P1(false, 0, false); }
         } else {
-            if (a.fmt == 1) { if (do_mix) WH_P1(true, 1, true); else WH_P1(true, 1, false); }
-            else            { if (do_mix) WH_P1(true, 0, true); else WH_P1(true, 0, false); }
+            // from the raw angles taken once per chunk (fm_rawdisc_kernel, with sum |x|^2)
+            fm_dispatch<FmFrontFast>(!interior, a.fmt, do_mix, a, fm_s, i_lo, W, n_lo, N, c, in_base, own_lo, own_hi, lane, wave,
+                                     p_fm, true);
         }
-#undef WH_P1
-#undef WH_P1X
-#undef WH_P1F
         __syncthreads();  // window (and, first time, taps) visible
 
         // phase 2: y[m0+o] = sum_i fm_s[o*down + i] * trev[i].
@@ -712,22 +689,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 5))) voi
         }
     }
     if (ROWS) return;   // (the rows' power sums were taken where the rows were made)
-    // block-reduce the two power sums (float64) and publish with one atomic pair
-    double db = p_base, df = p_fm;
-    for (int o = 32; o > 0; o >>= 1) {
-        db += __shfl_xor(db, o);
-        df += __shfl_xor(df, o);
-    }
-    if (lane == 0) {
-        red[wave] = db;
-        red[4 + wave] = df;
-    }
+    // block-reduce the sum of v^2 (float64) and publish it; sum |x|^2 is fm_rawdisc_kernel's
+    double df = p_fm;
+    for (int o = 32; o > 0; o >>= 1) df += __shfl_xor(df, o);
+    if (lane == 0) red[wave] = df;
     __syncthreads();
-    if (tid == 0) {
-        double *acc = a.acc + ((size_t)chunk * a.K + k) * 2;
-        if (k == 0 && a.araw == nullptr) atomicAdd(acc, red[0] + red[1] + red[2] + red[3]);   // shared by the chunk's channels (finalize); the fast front's pre-pass owns it
-        atomicAdd(acc + 1, red[4] + red[5] + red[6] + red[7]);
-    }
+    if (tid == 0) atomicAdd(a.acc + ((size_t)chunk * a.K + k) * 2 + 1, red[0] + red[1] + red[2] + red[3]);
 }
 
 // unfused first stage: NCO mix + demodulator front (FM discriminator / AM envelope / SSB product
@@ -747,20 +714,11 @@ __global__ __launch_bounds__(256) void chan_front_kernel(FmArgs a) {
     int b_hi = b_lo + per_block;
     if (b_hi > N) b_hi = N;
     if (a.demod == 0) {
-        // FM rows: the fused kernel's phase 1 (two samples per lane, packed arithmetic, hardware sin / cos, loads one step
-        // ahead) writing the row to memory instead of the LDS window -- window index == chunk index, this block owns
-        // [b_lo, b_hi)
+        // FM rows: fm_phase1 (two samples per lane, packed arithmetic, hardware sin / cos, loads one step ahead) writing
+        // the row to memory -- window index == chunk index, this block owns [b_lo, b_hi)
         double pb = 0.0, pf = 0.0;
         const bool interior = b_lo >= 2 && b_hi + 128 <= N;
-#define WH_F1(CHK, F, M) fm_phase1<CHK, F, M>(a, fm, b_lo, b_hi, 0, N, c, in_base, b_lo, b_hi, lane, wave, pb, pf, true)
-        if (interior) {
-            if (a.fmt == 1) { if (do_mix) WH_F1(false, 1, true); else WH_F1(false, 1, false); }
-            else            { if (do_mix) WH_F1(false, 0, true); else WH_F1(false, 0, false); }
-        } else {
-            if (a.fmt == 1) { if (do_mix) WH_F1(true, 1, true); else WH_F1(true, 1, false); }
-            else            { if (do_mix) WH_F1(true, 0, true); else WH_F1(true, 0, false); }
-        }
-#undef WH_F1
+        fm_dispatch<FmFront>(!interior, a.fmt, do_mix, a, fm, b_lo, b_hi, 0, N, c, in_base, b_lo, b_hi, lane, wave, pb, pf);
         for (int o = 32; o > 0; o >>= 1) {
             pb += __shfl_xor(pb, o);
             pf += __shfl_xor(pf, o);
@@ -787,13 +745,7 @@ __global__ __launch_bounds__(256) void chan_front_kernel(FmArgs a) {
         prv.y = __shfl_up(bse.y, 1);
         if (lane > 0 && valid && n < b_hi) {
             float v = 0.f;
-            if (a.demod == 0) {          // dsp/fm.py:65-97
-                if (n >= 1) {
-                    float re = bse.x * prv.x + bse.y * prv.y;
-                    float im = bse.y * prv.x - bse.x * prv.y;
-                    v = whm_atan2f(im, re) * a.scale;
-                }
-            } else if (a.demod == 1) {   // dsp/am.py:103 np.abs(iq)
+            if (a.demod == 1) {          // dsp/am.py:103 np.abs(iq)
                 v = hypotf(bse.x, bse.y);
             } else {                     // dsp/am.py:23-42, 204-210: BFO with float64 phase, + sign; real part
                 double t = (double)n / a.fs_d;

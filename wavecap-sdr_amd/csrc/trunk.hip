@@ -19,87 +19,7 @@ using namespace wh;
 
 namespace {
 
-struct DdcArgs {
-    const float2 *x;      // stage input (raw IQ for stage 1, decimated1 for stage 2)
-    const float2 *hist;   // [L-1] previous (mixed) inputs, oldest first
-    float2 *out;          // [n_out]
-    const double *taps;   // [L]
-    int L, D, n, n_out, opw;
-    int mix;              // 1: apply the NCO to x
-    int first;            // 1: history := first (mixed) sample (lfilter_zi * x[0])
-    double c1;            // (-2.0*np.pi) * offset_hz
-    double fs;
-    long long idx0;       // sample index of x[0]
-};
-
-__device__ __forceinline__ float2 ddc_mix(float2 v, const DdcArgs &a, long long i) {
-    if (!a.mix) return v;
-    // phase = -2.0*np.pi*offset_hz*n/sample_rate, left to right in float64 (system.py:1456-1457)
-    double nn = (double)(a.idx0 + i);
-    double ph = __ddiv_rn(__dmul_rn(a.c1, nn), a.fs);
-    double s, c;
-    sincos(ph, &s, &c);
-    float sr = (float)c, si = (float)s;   // np.exp(1j*phase).astype(complex64)
-    return make_float2(__fsub_rn(__fmul_rn(v.x, sr), __fmul_rn(v.y, si)),
-                       __fadd_rn(__fmul_rn(v.x, si), __fmul_rn(v.y, sr)));
-}
-
-__global__ __launch_bounds__(256) void ddc_stage_kernel(DdcArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char sm_raw[];
-    double *tp = reinterpret_cast<double *>(sm_raw);
-    float2 *tile = reinterpret_cast<float2 *>(sm_raw + (size_t)a.L * sizeof(double));
-    const int tid = threadIdx.x;
-    const int m0 = blockIdx.x * a.opw;
-    int mc = a.n_out - m0;
-    if (mc > a.opw) mc = a.opw;
-    const int H = a.L - 1;
-    const long long p0 = (long long)m0 * a.D - H;      // stream position of tile[0]
-    const int span = (mc - 1) * a.D + a.L;
-    for (int i = tid; i < a.L; i += 256) tp[i] = a.taps[i];
-    for (int i = tid; i < span; i += 256) {
-        long long p = p0 + i;
-        float2 v;
-        if (p >= 0) v = ddc_mix(a.x[p], a, p);
-        else if (a.first) v = ddc_mix(a.x[0], a, 0);
-        else v = a.hist[p + H];
-        tile[i] = v;
-    }
-    __syncthreads();
-    // 256/opw lanes share one output (opw is a power of two <= 256)
-    const int S = 256 / a.opw;
-    const int o = tid / S, sub = tid - o * S;
-    double ar = 0.0, ai = 0.0;
-    if (o < mc) {
-        const float2 *w = tile + o * a.D + H;
-        for (int k = sub; k < a.L; k += S) {
-            float2 v = w[-k];
-            double t = tp[k];
-            ar = fma(t, (double)v.x, ar);
-            ai = fma(t, (double)v.y, ai);
-        }
-    }
-    for (int w = 1; w < S; w <<= 1) {
-        ar += __shfl_xor(ar, w);
-        ai += __shfl_xor(ai, w);
-    }
-    if (o < mc && sub == 0) a.out[m0 + o] = make_float2((float)ar, (float)ai);
-}
-
-// new_hist[i] = (mixed) stream sample n - (L-1) + i
-__global__ __launch_bounds__(256) void ddc_carry_kernel(DdcArgs a, float2 *hist_new) {
-    const int H = a.L - 1;
-    int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= H) return;
-    long long p = (long long)a.n - H + i;
-    float2 v;
-    if (p >= 0) v = ddc_mix(a.x[p], a, p);
-    else if (a.first) v = ddc_mix(a.x[0], a, 0);
-    else v = a.hist[p + H];
-    hist_new[i] = v;
-}
-
-
-// ---- bank form of the front-end: K voice recorders / control monitors on ONE wideband buffer -------------
+// ---- the front-end: K voice recorders / control monitors on ONE wideband buffer (wh_ddc: K = 1) ----------
 // (trunking/system.py:453-656 VoiceRecorder.process_iq runs the same NCO + two lfilter/[::D] stages per recorder,
 // each with its own offset, sample index and filter state; inactive recorders are skipped and keep their state.)
 constexpr int DDC_BANK_MAX = 64;
@@ -107,7 +27,9 @@ constexpr int DDC_BANK_MAX = 64;
 struct DdcChan {
     double c1;            // (-2.0*np.pi) * offset_hz
     long long idx0;       // sample index of x[0]
-    int mix, first, active, cur;
+    int mix;              // 1: apply the NCO to x (stage 1 only)
+    int first;            // 1: history := first (mixed) sample (lfilter_zi * x[0])
+    int active, cur;
 };
 
 struct DdcBankArgs {
@@ -122,12 +44,23 @@ struct DdcBankArgs {
     DdcChan ch[DDC_BANK_MAX];
 };
 
+__device__ __forceinline__ float2 ddc_mix(float2 v, const DdcBankArgs &a, const DdcChan &c, long long i) {
+    if (a.stage2 || !c.mix) return v;
+    // phase = -2.0*np.pi*offset_hz*n/sample_rate, left to right in float64 (system.py:1456-1457)
+    double nn = (double)(c.idx0 + i);
+    double ph = __ddiv_rn(__dmul_rn(c.c1, nn), a.fs);
+    double s, co;
+    sincos(ph, &s, &co);
+    float sr = (float)co, si = (float)s;   // np.exp(1j*phase).astype(complex64)
+    return make_float2(__fsub_rn(__fmul_rn(v.x, sr), __fmul_rn(v.y, si)),
+                       __fadd_rn(__fmul_rn(v.x, si), __fmul_rn(v.y, sr)));
+}
+
+// (mixed) stream sample p of a channel; p < 0 reaches into the history (new_hist[i] = sample n - (L-1) + i)
 __device__ __forceinline__ float2 ddcb_fetch(const DdcBankArgs &a, const DdcChan &c, const float2 *x, const float2 *hist,
                                              long long p) {
-    DdcArgs m;            // reuse ddc_mix's arithmetic
-    m.mix = a.stage2 ? 0 : c.mix; m.c1 = c.c1; m.fs = a.fs; m.idx0 = c.idx0;
-    if (p >= 0) return ddc_mix(x[p], m, p);
-    if (c.first) return ddc_mix(x[0], m, 0);
+    if (p >= 0) return ddc_mix(x[p], a, c, p);
+    if (c.first) return ddc_mix(x[0], a, c, 0);
     return hist[p + (a.L - 1)];
 }
 
@@ -328,118 +261,7 @@ int pick_opw(int L, int D) {
 
 }  // namespace
 
-struct wh_ddc {
-    int fs, L1, D1, L2, D2, max_n;
-    double *d_t1 = nullptr, *d_t2 = nullptr;
-    float2 *d_h1[2] = {nullptr, nullptr}, *d_h2[2] = {nullptr, nullptr};
-    float2 *d_mid = nullptr;
-    int cur = 0;
-    bool first = true;
-    long long sample_idx = 0;
-    double last_offset = 0.0;
-};
-
-extern "C" int wh_ddc_create(wh_ddc **out, int sample_rate, const double *h_taps1, int n1, int d1,
-                             const double *h_taps2, int n2, int d2, int max_samples_per_call) {
-    if (!out || !h_taps1 || n1 < 1 || d1 < 1 || sample_rate < 1 || max_samples_per_call < 1 || n1 > 4096 ||
-        (d2 > 1 && (!h_taps2 || n2 < 1 || n2 > 4096)))
-        return set_err(WH_E_ARG, "wh_ddc_create: bad arguments");
-    wh_ddc *d = new wh_ddc();
-    std::unique_ptr<wh_ddc, void (*)(wh_ddc *)> guard(d, wh_ddc_destroy);  // frees partial state on early return
-    d->fs = sample_rate; d->L1 = n1; d->D1 = d1; d->L2 = d2 > 1 ? n2 : 0; d->D2 = d2 > 1 ? d2 : 1;
-    d->max_n = max_samples_per_call;
-    WH_HIP(hipMalloc(&d->d_t1, n1 * sizeof(double)));
-    WH_HIP(hipMemcpy(d->d_t1, h_taps1, n1 * sizeof(double), hipMemcpyHostToDevice));
-    for (int i = 0; i < 2; ++i) WH_HIP(hipMalloc(&d->d_h1[i], (size_t)(n1 > 1 ? n1 - 1 : 1) * sizeof(float2)));
-    if (d->L2) {
-        WH_HIP(hipMalloc(&d->d_t2, n2 * sizeof(double)));
-        WH_HIP(hipMemcpy(d->d_t2, h_taps2, n2 * sizeof(double), hipMemcpyHostToDevice));
-        for (int i = 0; i < 2; ++i) WH_HIP(hipMalloc(&d->d_h2[i], (size_t)(n2 > 1 ? n2 - 1 : 1) * sizeof(float2)));
-        WH_HIP(hipMalloc(&d->d_mid, ((size_t)max_samples_per_call / d1 + 2) * sizeof(float2)));
-    }
-    *out = guard.release();
-    return WH_OK;
-}
-
-extern "C" void wh_ddc_destroy(wh_ddc *d) {
-    if (!d) return;
-    (void)hipFree(d->d_t1); (void)hipFree(d->d_t2); (void)hipFree(d->d_mid);
-    for (int i = 0; i < 2; ++i) { (void)hipFree(d->d_h1[i]); (void)hipFree(d->d_h2[i]); }
-    delete d;
-}
-
-extern "C" int wh_ddc_reset(wh_ddc *d) {   /* overflow recovery, system.py:1574-1588 */
-    if (!d) return set_err(WH_E_ARG, "wh_ddc_reset: null handle");
-    d->first = true;
-    d->sample_idx = 0;
-    d->last_offset = 0.0;
-    return WH_OK;
-}
-
-extern "C" size_t wh_ddc_out_len(const wh_ddc *d, size_t n) {
-    if (!d || n == 0) return 0;
-    size_t n1 = (n + d->D1 - 1) / d->D1;
-    return (n1 + d->D2 - 1) / d->D2;
-}
-
-static int ddc_launch(const DdcArgs &a0, float2 *hist_new, hipStream_t st) {
-    DdcArgs a = a0;
-    a.opw = pick_opw(a.L, a.D);
-    size_t smem = (size_t)a.L * sizeof(double) + (size_t)((a.opw - 1) * a.D + a.L) * sizeof(float2);
-    if (smem > 64 * 1024) return set_err(WH_E_ARG, "ddc: decimation %d x %d taps does not fit the LDS tile", a.D, a.L);
-    unsigned blocks = (unsigned)((a.n_out + a.opw - 1) / a.opw);
-    hipLaunchKernelGGL(ddc_stage_kernel, dim3(blocks), dim3(256), smem, st, a);
-    WH_LAUNCH_CHECK();
-    if (a.L > 1) {
-        hipLaunchKernelGGL(ddc_carry_kernel, dim3((a.L - 1 + 255) / 256), dim3(256), 0, st, a, hist_new);
-        WH_LAUNCH_CHECK();
-    }
-    return WH_OK;
-}
-
-extern "C" int wh_ddc_run(wh_ddc *d, const float *d_iq, size_t n, double offset_hz, float *d_out, void *stream) {
-    if (!d) return set_err(WH_E_ARG, "wh_ddc_run: null handle");
-    if (n == 0) return WH_OK;
-    if (!d_iq || !d_out) return set_err(WH_E_ARG, "wh_ddc_run: null buffer");
-    if (n > (size_t)d->max_n) return set_err(WH_E_ARG, "wh_ddc_run: n exceeds max_samples_per_call");
-    hipStream_t st = as_stream(stream);
-    const bool mix = offset_hz != 0.0;
-    if (mix && offset_hz != d->last_offset) {   // system.py:1450-1452
-        d->sample_idx = 0;
-        d->last_offset = offset_hz;
-    }
-    const int n1 = (int)((n + d->D1 - 1) / d->D1);
-    DdcArgs a;
-    a.x = reinterpret_cast<const float2 *>(d_iq);
-    a.hist = d->d_h1[d->cur];
-    a.out = d->L2 ? d->d_mid : reinterpret_cast<float2 *>(d_out);
-    a.taps = d->d_t1; a.L = d->L1; a.D = d->D1; a.n = (int)n; a.n_out = n1; a.opw = 0;
-    a.mix = mix ? 1 : 0; a.first = d->first ? 1 : 0;
-    a.c1 = (-2.0 * M_PI) * offset_hz;
-    a.fs = (double)d->fs;
-    a.idx0 = d->sample_idx;
-    int rc = ddc_launch(a, d->d_h1[d->cur ^ 1], st);
-    if (rc != WH_OK) return rc;
-    if (d->L2) {
-        DdcArgs b;
-        b.x = d->d_mid;
-        b.hist = d->d_h2[d->cur];
-        b.out = reinterpret_cast<float2 *>(d_out);
-        b.taps = d->d_t2; b.L = d->L2; b.D = d->D2; b.n = n1; b.n_out = (n1 + d->D2 - 1) / d->D2; b.opw = 0;
-        b.mix = 0; b.first = d->first ? 1 : 0; b.c1 = 0.0; b.fs = 1.0; b.idx0 = 0;
-        rc = ddc_launch(b, d->d_h2[d->cur ^ 1], st);
-        if (rc != WH_OK) return rc;
-    }
-    d->cur ^= 1;
-    d->first = false;
-    if (mix) {   // system.py:1461-1466
-        d->sample_idx += (long long)n;
-        if (d->sample_idx >= d->fs) d->sample_idx %= d->fs;
-    }
-    return WH_OK;
-}
-
-// ---- wh_ddc_bank ---------------------------------------------------------------------------------
+// ---- wh_ddc_bank, and wh_ddc as a bank of one ---------------------------------------------------
 struct wh_ddc_bank {
     int K, fs, L1, D1, L2, D2, max_n;
     double *d_t1 = nullptr, *d_t2 = nullptr;
@@ -448,38 +270,45 @@ struct wh_ddc_bank {
     size_t mid_stride = 0;
     struct Chan { bool first = true; long long sample_idx = 0; double last_offset = 0.0; int cur = 0; };
     std::vector<Chan> ch;
+    ~wh_ddc_bank() {
+        (void)hipFree(d_t1); (void)hipFree(d_t2); (void)hipFree(d_mid);
+        for (int i = 0; i < 2; ++i) { (void)hipFree(d_h1[i]); (void)hipFree(d_h2[i]); }
+    }
 };
+
+struct wh_ddc : wh_ddc_bank {};
+
+// arguments checked by the caller; a stage of one tap (wh_ddc only) has no history to carry
+static int ddc_bank_init(wh_ddc_bank *d, int n_channels, int sample_rate, const double *h_taps1, int n1, int d1,
+                         const double *h_taps2, int n2, int d2, int max_samples_per_call) {
+    d->K = n_channels; d->fs = sample_rate; d->L1 = n1; d->D1 = d1; d->L2 = d2 > 1 ? n2 : 0; d->D2 = d2 > 1 ? d2 : 1;
+    d->max_n = max_samples_per_call;
+    d->ch.resize(n_channels);
+    WH_HIP(hipMalloc(&d->d_t1, n1 * sizeof(double)));
+    WH_HIP(hipMemcpy(d->d_t1, h_taps1, n1 * sizeof(double), hipMemcpyHostToDevice));
+    for (int i = 0; i < 2; ++i) WH_HIP(hipMalloc(&d->d_h1[i], (size_t)n_channels * (n1 > 1 ? n1 - 1 : 1) * sizeof(float2)));
+    if (d->L2) {
+        WH_HIP(hipMalloc(&d->d_t2, n2 * sizeof(double)));
+        WH_HIP(hipMemcpy(d->d_t2, h_taps2, n2 * sizeof(double), hipMemcpyHostToDevice));
+        for (int i = 0; i < 2; ++i) WH_HIP(hipMalloc(&d->d_h2[i], (size_t)n_channels * (n2 > 1 ? n2 - 1 : 1) * sizeof(float2)));
+        d->mid_stride = (size_t)max_samples_per_call / d1 + 2;
+        WH_HIP(hipMalloc(&d->d_mid, (size_t)n_channels * d->mid_stride * sizeof(float2)));
+    }
+    return WH_OK;
+}
 
 extern "C" int wh_ddc_bank_create(wh_ddc_bank **out, int n_channels, int sample_rate, const double *h_taps1, int n1, int d1,
                                   const double *h_taps2, int n2, int d2, int max_samples_per_call) {
     if (!out || !h_taps1 || n_channels < 1 || n_channels > DDC_BANK_MAX || n1 < 2 || d1 < 1 || sample_rate < 1 ||
         max_samples_per_call < 1 || n1 > 4096 || (d2 > 1 && (!h_taps2 || n2 < 2 || n2 > 4096)))
         return set_err(WH_E_ARG, "wh_ddc_bank_create: bad arguments (1..%d channels)", DDC_BANK_MAX);
-    wh_ddc_bank *d = new wh_ddc_bank();
-    std::unique_ptr<wh_ddc_bank, void (*)(wh_ddc_bank *)> guard(d, wh_ddc_bank_destroy);  // frees partial state on early return
-    d->K = n_channels; d->fs = sample_rate; d->L1 = n1; d->D1 = d1; d->L2 = d2 > 1 ? n2 : 0; d->D2 = d2 > 1 ? d2 : 1;
-    d->max_n = max_samples_per_call;
-    d->ch.resize(n_channels);
-    WH_HIP(hipMalloc(&d->d_t1, n1 * sizeof(double)));
-    WH_HIP(hipMemcpy(d->d_t1, h_taps1, n1 * sizeof(double), hipMemcpyHostToDevice));
-    for (int i = 0; i < 2; ++i) WH_HIP(hipMalloc(&d->d_h1[i], (size_t)n_channels * (n1 - 1) * sizeof(float2)));
-    if (d->L2) {
-        WH_HIP(hipMalloc(&d->d_t2, n2 * sizeof(double)));
-        WH_HIP(hipMemcpy(d->d_t2, h_taps2, n2 * sizeof(double), hipMemcpyHostToDevice));
-        for (int i = 0; i < 2; ++i) WH_HIP(hipMalloc(&d->d_h2[i], (size_t)n_channels * (n2 - 1) * sizeof(float2)));
-        d->mid_stride = (size_t)max_samples_per_call / d1 + 2;
-        WH_HIP(hipMalloc(&d->d_mid, (size_t)n_channels * d->mid_stride * sizeof(float2)));
-    }
-    *out = guard.release();
-    return WH_OK;
+    std::unique_ptr<wh_ddc_bank> d(new wh_ddc_bank());   // frees partial state on early return
+    const int rc = ddc_bank_init(d.get(), n_channels, sample_rate, h_taps1, n1, d1, h_taps2, n2, d2, max_samples_per_call);
+    if (rc == WH_OK) *out = d.release();
+    return rc;
 }
 
-extern "C" void wh_ddc_bank_destroy(wh_ddc_bank *d) {
-    if (!d) return;
-    (void)hipFree(d->d_t1); (void)hipFree(d->d_t2); (void)hipFree(d->d_mid);
-    for (int i = 0; i < 2; ++i) { (void)hipFree(d->d_h1[i]); (void)hipFree(d->d_h2[i]); }
-    delete d;
-}
+extern "C" void wh_ddc_bank_destroy(wh_ddc_bank *d) { delete d; }
 
 extern "C" int wh_ddc_bank_reset(wh_ddc_bank *d, int channel) {
     if (!d || channel < -1 || channel >= d->K) return set_err(WH_E_ARG, "wh_ddc_bank_reset: bad arguments");
@@ -501,11 +330,13 @@ extern "C" size_t wh_ddc_bank_out_len(const wh_ddc_bank *d, size_t n) {
 static int ddcb_launch(DdcBankArgs &a, int K, hipStream_t st) {
     a.opw = pick_opw(a.L, a.D);
     size_t smem = (size_t)a.L * sizeof(double) + (size_t)((a.opw - 1) * a.D + a.L) * sizeof(float2);
-    if (smem > 64 * 1024) return set_err(WH_E_ARG, "ddc bank: decimation %d x %d taps does not fit the LDS tile", a.D, a.L);
+    if (smem > 64 * 1024) return set_err(WH_E_ARG, "ddc: decimation %d x %d taps does not fit the LDS tile", a.D, a.L);
     hipLaunchKernelGGL(ddcb_stage_kernel, dim3((unsigned)((a.n_out + a.opw - 1) / a.opw), K), dim3(256), smem, st, a);
     WH_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ddcb_carry_kernel, dim3((a.L - 1 + 255) / 256, K), dim3(256), 0, st, a);
-    WH_LAUNCH_CHECK();
+    if (a.L > 1) {
+        hipLaunchKernelGGL(ddcb_carry_kernel, dim3((a.L - 1 + 255) / 256, K), dim3(256), 0, st, a);
+        WH_LAUNCH_CHECK();
+    }
     return WH_OK;
 }
 
@@ -565,6 +396,34 @@ extern "C" int wh_ddc_bank_run(wh_ddc_bank *d, const float *d_iq, size_t n, cons
         }
     }
     return WH_OK;
+}
+
+extern "C" int wh_ddc_create(wh_ddc **out, int sample_rate, const double *h_taps1, int n1, int d1,
+                             const double *h_taps2, int n2, int d2, int max_samples_per_call) {
+    if (!out || !h_taps1 || n1 < 1 || d1 < 1 || sample_rate < 1 || max_samples_per_call < 1 || n1 > 4096 ||
+        (d2 > 1 && (!h_taps2 || n2 < 1 || n2 > 4096)))
+        return set_err(WH_E_ARG, "wh_ddc_create: bad arguments");
+    std::unique_ptr<wh_ddc> d(new wh_ddc());
+    const int rc = ddc_bank_init(d.get(), 1, sample_rate, h_taps1, n1, d1, h_taps2, n2, d2, max_samples_per_call);
+    if (rc == WH_OK) *out = d.release();
+    return rc;
+}
+
+extern "C" void wh_ddc_destroy(wh_ddc *d) { delete d; }
+
+extern "C" int wh_ddc_reset(wh_ddc *d) {   /* overflow recovery, system.py:1574-1588 */
+    if (!d) return set_err(WH_E_ARG, "wh_ddc_reset: null handle");
+    return wh_ddc_bank_reset(d, 0);
+}
+
+extern "C" size_t wh_ddc_out_len(const wh_ddc *d, size_t n) { return wh_ddc_bank_out_len(d, n); }
+
+extern "C" int wh_ddc_run(wh_ddc *d, const float *d_iq, size_t n, double offset_hz, float *d_out, void *stream) {
+    if (!d) return set_err(WH_E_ARG, "wh_ddc_run: null handle");
+    if (n == 0) return WH_OK;
+    if (!d_iq || !d_out) return set_err(WH_E_ARG, "wh_ddc_run: null buffer");
+    if (n > (size_t)d->max_n) return set_err(WH_E_ARG, "wh_ddc_run: n exceeds max_samples_per_call");
+    return wh_ddc_bank_run(d, d_iq, n, &offset_hz, nullptr, d_out, wh_ddc_bank_out_len(d, n), stream);
 }
 
 extern "C" int wh_scan_measure(const float *d_iq, size_t n, int sample_rate, const int *h_offsets_hz, int n_off,

@@ -191,6 +191,22 @@ def check(status: int, what: str = "") -> None:
         raise RuntimeError(f"libwavehip {what} failed ({status}): {msg}")
 
 
+class Handle:
+    """Base of the classes that own one library handle: `_create("wh_x", *args)` calls wh_x_create(&h, *args) and
+    raises on failure; the object's finalizer calls wh_x_destroy(h)."""
+
+    def _create(self, prefix: str, *args) -> None:
+        self._h = c_void_p()
+        self._destroy = getattr(lib, prefix + "_destroy")
+        check(getattr(lib, prefix + "_create")(C.byref(self._h), *args), prefix + "_create")
+
+    def __del__(self):
+        h, destroy = getattr(self, "_h", None), getattr(self, "_destroy", None)
+        if h and destroy:
+            destroy(h)
+            self._h = None
+
+
 def dptr(arr, dtype: str) -> C.POINTER:
     """Host numpy array -> typed ctypes pointer (keeps no reference: caller holds the array)."""
     import numpy as np

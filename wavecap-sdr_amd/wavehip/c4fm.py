@@ -18,7 +18,6 @@ SDRTrunk constants) ships as a binary data file."""
 
 from __future__ import annotations
 
-import ctypes as C
 import os
 
 import numpy as np
@@ -59,7 +58,7 @@ def design_rrc_filter(samples_per_symbol: float, num_taps: int = 101, alpha: flo
     return (h / np.sum(h)).astype(np.float32)
 
 
-class C4FMBank:
+class C4FMBank(_lib.Handle):
     """C independent C4FM demodulators, one wavefront each for the feedback part."""
 
     def __init__(self, n_channels: int, sample_rate: int = 19200, symbol_rate: int = SYMBOL_RATE,
@@ -76,13 +75,10 @@ class C4FMBank:
                                              num_taps=int(16 * self.samples_per_symbol) + 1, alpha=alpha)
         taps = np.ascontiguousarray(np.load(_TAPS_FILE), dtype=np.float32)
         assert taps.shape == (129, 8)
-        self._h = C.c_void_p()
-        self._destroy = _lib.lib.wh_c4fm_bank_destroy
-        _lib.check(_lib.lib.wh_c4fm_bank_create(
-            C.byref(self._h), self.n_channels, float(self.samples_per_symbol),
-            _lib.dptr(self._baseband_lpf, "f32"), len(self._baseband_lpf),
-            _lib.dptr(self._rrc_filter, "f32"), len(self._rrc_filter), _lib.dptr(taps, "f32"),
-            self.max_samples_per_call), "wh_c4fm_bank_create")
+        self._create("wh_c4fm_bank", self.n_channels, float(self.samples_per_symbol),
+                     _lib.dptr(self._baseband_lpf, "f32"), len(self._baseband_lpf),
+                     _lib.dptr(self._rrc_filter, "f32"), len(self._rrc_filter), _lib.dptr(taps, "f32"),
+                     self.max_samples_per_call)
         self._counts = self._torch.zeros(self.n_channels, dtype=self._torch.int32, device="cuda")
         self._size_outputs()
 
@@ -101,12 +97,6 @@ class C4FMBank:
                    "wh_c4fm_bank_reserve")
         self.max_samples_per_call = int(max_samples_per_call)
         self._size_outputs()
-
-    def __del__(self):
-        h, destroy = getattr(self, "_h", None), getattr(self, "_destroy", None)
-        if h and destroy:
-            destroy(h)
-            self._h = None
 
     def reset(self) -> None:
         _lib.check(_lib.lib.wh_c4fm_bank_reset(self._h, _lib.stream_ptr(self._torch)), "wh_c4fm_bank_reset")

@@ -273,7 +273,7 @@ def _squelch_key(cfgs) -> tuple:
     return tuple(None if getattr(c, "squelch_db", None) is None else float(c.squelch_db) for c in cfgs)
 
 
-class ChannelBank:
+class ChannelBank(_lib.Handle):
     """All channels of one capture that share one chain (mode + filter settings + audio rate)."""
 
     def __init__(self, sample_rate: int, chunk_len: int, cfgs: list, input_format: str = "cf32",
@@ -363,16 +363,8 @@ class ChannelBank:
             cfg.h_taps = _lib.dptr(h, "f64")
             cfg.ntaps, cfg.up, cfg.down, cfg.d0 = len(h), up, down, d0
         cfg.n_out = self.n_out
-        self._h = C.c_void_p()
-        self._destroy = _lib.lib.wh_chanbank_destroy
-        _lib.check(_lib.lib.wh_chanbank_create(C.byref(self._h), C.byref(cfg)), "wh_chanbank_create")
+        self._create("wh_chanbank", C.byref(cfg))
         del keep
-
-    def __del__(self):
-        h, destroy = getattr(self, "_h", None), getattr(self, "_destroy", None)
-        if h and destroy:
-            destroy(h)
-            self._h = None
 
     def set_offsets(self, offsets_hz) -> None:
         """Retune the bank's channels (API PATCH of offset_hz -> capture.py:442-501; the reference's operator reads

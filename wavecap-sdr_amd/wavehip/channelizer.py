@@ -20,7 +20,7 @@ DEFAULT_CHANNEL_BANDWIDTH = 25000
 DEFAULT_TAPS_PER_CHANNEL = 9
 
 
-class PolyphaseChannelizer:
+class PolyphaseChannelizer(_lib.Handle):
     def __init__(self, sample_rate: float, channel_bandwidth: int = DEFAULT_CHANNEL_BANDWIDTH,
                  taps_per_channel: int = DEFAULT_TAPS_PER_CHANNEL):
         self.sample_rate = sample_rate
@@ -34,11 +34,8 @@ class PolyphaseChannelizer:
         self._design_filter()
         self.block_counter = 0
         self._torch = _lib.require_gpu()
-        self._h = C.c_void_p()
-        self._destroy = _lib.lib.wh_pfb_destroy
         arms = np.ascontiguousarray(self.arms, dtype=np.float64)
-        _lib.check(_lib.lib.wh_pfb_create(C.byref(self._h), self.channel_count, self.taps_per_channel,
-                                          _lib.dptr(arms, "f64")), "wh_pfb_create")
+        self._create("wh_pfb", self.channel_count, self.taps_per_channel, _lib.dptr(arms, "f64"))
 
     def _design_filter(self) -> None:
         """channelizer.py:69-89 (same scipy call -> identical prototype taps)."""
@@ -49,12 +46,6 @@ class PolyphaseChannelizer:
         for arm in range(M):
             t = proto[arm::M]
             self.arms[arm, : len(t)] = t
-
-    def __del__(self):
-        h, destroy = getattr(self, "_h", None), getattr(self, "_destroy", None)
-        if h and destroy:
-            destroy(h)
-            self._h = None
 
     # -- carried state ---------------------------------------------------------------------
     @property

@@ -8,7 +8,6 @@ both algorithms are per-sample feedback loops).  Float64 throughout, like the re
 
 from __future__ import annotations
 
-import ctypes as C
 
 import numpy as np
 from scipy import signal
@@ -42,7 +41,7 @@ def design_rrc_filter_phase2(samples_per_symbol: float, num_taps: int = 65, alph
     return np.asarray(h / np.sqrt(np.sum(h ** 2)), dtype=np.float32)
 
 
-class CQPSKBank:
+class CQPSKBank(_lib.Handle):
     def __init__(self, n_channels: int, sample_rate: int = 48000, symbol_rate: int = 12000, rrc_alpha: float = 1.0,
                  rrc_taps: int = 65, carrier_loop_bw: float = 0.01, timing_loop_bw: float = 0.01,
                  max_samples_per_call: int = 1 << 16):
@@ -55,12 +54,8 @@ class CQPSKBank:
         zi = np.ascontiguousarray(signal.lfilter_zi(self._rrc, 1.0), dtype=np.float64)
         ckp, cki = calculate_loop_coefficients(0.0, carrier_loop_bw, 0.707)      # cqpsk.py:107-110
         tkp, tki = calculate_loop_coefficients(self.samples_per_symbol, timing_loop_bw, 1.0)
-        self._h = C.c_void_p()
-        self._destroy = _lib.lib.wh_cqpsk_bank_destroy
-        _lib.check(_lib.lib.wh_cqpsk_bank_create(C.byref(self._h), self.n_channels, float(self.samples_per_symbol),
-                                                 _lib.dptr(self._rrc, "f32"), len(self._rrc), _lib.dptr(zi, "f64"),
-                                                 ckp, cki, 0.1, tkp, tki, self.max_samples_per_call),
-                   "wh_cqpsk_bank_create")
+        self._create("wh_cqpsk_bank", self.n_channels, float(self.samples_per_symbol), _lib.dptr(self._rrc, "f32"),
+                     len(self._rrc), _lib.dptr(zi, "f64"), ckp, cki, 0.1, tkp, tki, self.max_samples_per_call)
         self._counts = self._torch.zeros(self.n_channels, dtype=self._torch.int32, device="cuda")
         self._symbols = None
         self._size_outputs()
@@ -79,12 +74,6 @@ class CQPSKBank:
                    "wh_cqpsk_bank_reserve")
         self.max_samples_per_call = int(max_samples_per_call)
         self._size_outputs()
-
-    def __del__(self):
-        h, destroy = getattr(self, "_h", None), getattr(self, "_destroy", None)
-        if h and destroy:
-            destroy(h)
-            self._h = None
 
     def reset(self) -> None:
         _lib.check(_lib.lib.wh_cqpsk_bank_reset(self._h, _lib.stream_ptr(self._torch)), "wh_cqpsk_bank_reset")
@@ -140,22 +129,13 @@ class CQPSKDemodulator:
         return self._bank.demodulate(np.asarray(iq)[None, :])[0]
 
 
-class GardnerBank:
+class GardnerBank(_lib.Handle):
     def __init__(self, n_channels: int, samples_per_symbol: float, loop_bw: float = 0.01, damping: float = 1.0):
         self._torch = _lib.require_gpu()
         self.n_channels = int(n_channels)
         self.samples_per_symbol = float(samples_per_symbol)
         kp, ki = calculate_loop_coefficients(samples_per_symbol, loop_bw, damping)
-        self._h = C.c_void_p()
-        self._destroy = _lib.lib.wh_gardner_bank_destroy
-        _lib.check(_lib.lib.wh_gardner_bank_create(C.byref(self._h), self.n_channels, self.samples_per_symbol, kp, ki),
-                   "wh_gardner_bank_create")
-
-    def __del__(self):
-        h, destroy = getattr(self, "_h", None), getattr(self, "_destroy", None)
-        if h and destroy:
-            destroy(h)
-            self._h = None
+        self._create("wh_gardner_bank", self.n_channels, self.samples_per_symbol, kp, ki)
 
     def reset(self) -> None:
         _lib.check(_lib.lib.wh_gardner_bank_reset(self._h, _lib.stream_ptr(self._torch)), "wh_gardner_bank_reset")
@@ -195,7 +175,7 @@ class GardnerTED:
         return s[0, :k].cpu().numpy(), e[0, :k].cpu().numpy()
 
 
-class CostasBank:
+class CostasBank(_lib.Handle):
     """CostasLoop (cqpsk.py:84-196) for C channels at once: complex128 [C, n] in -> phase-corrected complex128 [C, n]."""
 
     def __init__(self, n_channels: int, loop_bw: float = 0.01, damping: float = 0.707, max_freq: float = 0.1):
@@ -203,16 +183,7 @@ class CostasBank:
         self.n_channels = int(n_channels)
         self._kp, self._ki = calculate_loop_coefficients(0.0, loop_bw, damping)     # cqpsk.py:107-110
         self._max_freq = max_freq
-        self._h = C.c_void_p()
-        self._destroy = _lib.lib.wh_costas_bank_destroy
-        _lib.check(_lib.lib.wh_costas_bank_create(C.byref(self._h), self.n_channels, self._kp, self._ki, float(max_freq)),
-                   "wh_costas_bank_create")
-
-    def __del__(self):
-        h, destroy = getattr(self, "_h", None), getattr(self, "_destroy", None)
-        if h and destroy:
-            destroy(h)
-            self._h = None
+        self._create("wh_costas_bank", self.n_channels, self._kp, self._ki, float(max_freq))
 
     def reset(self) -> None:
         _lib.check(_lib.lib.wh_costas_bank_reset(self._h, _lib.stream_ptr(self._torch)), "wh_costas_bank_reset")
@@ -259,7 +230,7 @@ class CostasLoop:
         return float(self._bank.frequency_offsets()[0])
 
 
-class MuellerMullerBank:
+class MuellerMullerBank(_lib.Handle):
     """MuellerMullerTED (symbol_timing.py:214-380) for C channels: complex128 [C, n] -> (symbols, decisions complex128
     [C, cap], errors float64 [C, cap], counts int32 [C]) on the GPU."""
 
@@ -268,16 +239,7 @@ class MuellerMullerBank:
         self.n_channels = int(n_channels)
         self.samples_per_symbol = samples_per_symbol
         self._kp, self._ki = calculate_loop_coefficients(samples_per_symbol, loop_bw, damping)
-        self._h = C.c_void_p()
-        self._destroy = _lib.lib.wh_mm_bank_destroy
-        _lib.check(_lib.lib.wh_mm_bank_create(C.byref(self._h), self.n_channels, float(samples_per_symbol), self._kp, self._ki),
-                   "wh_mm_bank_create")
-
-    def __del__(self):
-        h, destroy = getattr(self, "_h", None), getattr(self, "_destroy", None)
-        if h and destroy:
-            destroy(h)
-            self._h = None
+        self._create("wh_mm_bank", self.n_channels, float(samples_per_symbol), self._kp, self._ki)
 
     def reset(self) -> None:
         _lib.check(_lib.lib.wh_mm_bank_reset(self._h, _lib.stream_ptr(self._torch)), "wh_mm_bank_reset")

@@ -8,7 +8,6 @@ workgroup per word, the 512 KiB table stays in L2) -- identical (data, error-cou
 
 from __future__ import annotations
 
-import ctypes as C
 
 import numpy as np
 
@@ -40,19 +39,11 @@ def pack_bits(bits) -> np.ndarray:
     return w
 
 
-class BCHDecoder:
+class BCHDecoder(_lib.Handle):
     def __init__(self):
         self._torch = _lib.require_gpu()
         self._table = np.ascontiguousarray(codeword_table())
-        self._h = C.c_void_p()
-        self._destroy = _lib.lib.wh_bch_destroy
-        _lib.check(_lib.lib.wh_bch_create(C.byref(self._h), self._table.ctypes.data), "wh_bch_create")
-
-    def __del__(self):
-        h, destroy = getattr(self, "_h", None), getattr(self, "_destroy", None)
-        if h and destroy:
-            destroy(h)
-            self._h = None
+        self._create("wh_bch", self._table.ctypes.data)
 
     def decode_device(self, words_dev, tracked_dev=None):
         """words_dev int64/uint64 GPU tensor [n] (63-bit words) -> (data int32 [n], errors int32 [n]) on the GPU."""

@@ -13,11 +13,12 @@ instance passes `isinstance(x, wavecapsdr.dsp.fft.base.FFTBackend)`.
 
 from __future__ import annotations
 
-import ctypes as C
 from abc import ABC, abstractmethod
 from dataclasses import dataclass
 
 import numpy as np
+
+from ._lib import Handle
 
 try:  # drop-in: subclass the reference's own ABC when it is there
     from wavecapsdr.dsp.fft.base import FFTBackend, FFTResult  # type: ignore
@@ -64,7 +65,7 @@ def is_available() -> bool:
         return False
 
 
-class HipFFTBackend(FFTBackend):
+class HipFFTBackend(FFTBackend, Handle):
     """MI355X spectrum backend (window + FFT + |.| + fftshift + log10 fused in one HIP kernel)."""
 
     def __init__(self, fft_size: int = 2048, engine: str = "fused"):
@@ -85,18 +86,10 @@ class HipFFTBackend(FFTBackend):
             raise ImportError("wavehip HIP backend unavailable: no ROCm GPU")
         super().__init__(fft_size)
         self._lib, self._torch = _lib, torch
-        self._h = C.c_void_p()
-        self._destroy = _lib.lib.wh_spectrum_destroy
-        _lib.check(_lib.lib.wh_spectrum_create(C.byref(self._h), int(fft_size)), "wh_spectrum_create")
+        self._create("wh_spectrum", int(fft_size))
         if engine in ("stockham", "shaped"):
             _lib.check(_lib.lib.wh_spectrum_tune(self._h, 1, 1 if engine == "stockham" else 2), "wh_spectrum_tune")
         self._freq_cache: dict[int, np.ndarray] = {}
-
-    def __del__(self):
-        h, destroy = getattr(self, "_h", None), getattr(self, "_destroy", None)
-        if h and destroy:
-            destroy(h)
-            self._h = None
 
     def _freqs(self, sample_rate: int) -> np.ndarray:
         f = self._freq_cache.get(sample_rate)

@@ -44,7 +44,7 @@ def generate_mmse_taps() -> np.ndarray:
     return taps
 
 
-class LSMBank:
+class LSMBank(_lib.Handle):
     def __init__(self, n_channels: int, sample_rate: int = 19200, symbol_rate: int = 4800,
                  max_samples_per_call: int = 1 << 17):
         self._torch = _lib.require_gpu()
@@ -54,22 +54,13 @@ class LSMBank:
         self.max_samples_per_call = int(max_samples_per_call)
         self._baseband_taps = np.ascontiguousarray(design_baseband_filter(sample_rate))
         self._mmse_taps = np.ascontiguousarray(generate_mmse_taps())
-        self._h = C.c_void_p()
-        self._destroy = _lib.lib.wh_lsm_bank_destroy
-        _lib.check(_lib.lib.wh_lsm_bank_create(C.byref(self._h), self.n_channels, float(self.samples_per_symbol),
-                                               _lib.dptr(self._baseband_taps, "f32"), _lib.dptr(self._mmse_taps, "f32"),
-                                               self.max_samples_per_call), "wh_lsm_bank_create")
+        self._create("wh_lsm_bank", self.n_channels, float(self.samples_per_symbol), _lib.dptr(self._baseband_taps, "f32"),
+                     _lib.dptr(self._mmse_taps, "f32"), self.max_samples_per_call)
         torch = self._torch
         self.cap = self.max_samples_per_call            # at most one symbol per sample
         self._dibits = torch.empty((self.n_channels, self.cap), dtype=torch.uint8, device="cuda")
         self._phases = None
         self._counts = torch.zeros(self.n_channels, dtype=torch.int32, device="cuda")
-
-    def __del__(self):
-        h, destroy = getattr(self, "_h", None), getattr(self, "_destroy", None)
-        if h and destroy:
-            destroy(h)
-            self._h = None
 
     def reset(self) -> None:
         _lib.check(_lib.lib.wh_lsm_bank_reset(self._h, _lib.stream_ptr(self._torch)), "wh_lsm_bank_reset")

@@ -51,7 +51,7 @@ def recorder_decimation_plan(sample_rate: int, target_rate: int = 48000) -> tupl
     return total, 1
 
 
-class TrunkingDDC:
+class TrunkingDDC(_lib.Handle):
     def __init__(self, sample_rate: int, stage1_factor: int | None = None, stage2_factor: int | None = None,
                  max_samples_per_call: int = 1 << 20):
         self._torch = _lib.require_gpu()
@@ -66,17 +66,8 @@ class TrunkingDDC:
         self.output_rate = self.sample_rate // self.stage1_factor // self.stage2_factor
         t1 = np.ascontiguousarray(self.stage1_taps, dtype=np.float64)
         t2 = np.ascontiguousarray(self.stage2_taps, dtype=np.float64)
-        self._h = C.c_void_p()
-        self._destroy = _lib.lib.wh_ddc_destroy
-        _lib.check(_lib.lib.wh_ddc_create(C.byref(self._h), self.sample_rate, _lib.dptr(t1, "f64"), len(t1),
-                                          self.stage1_factor, _lib.dptr(t2, "f64"), len(t2), self.stage2_factor,
-                                          int(max_samples_per_call)), "wh_ddc_create")
-
-    def __del__(self):
-        h, destroy = getattr(self, "_h", None), getattr(self, "_destroy", None)
-        if h and destroy:
-            destroy(h)
-            self._h = None
+        self._create("wh_ddc", self.sample_rate, _lib.dptr(t1, "f64"), len(t1), self.stage1_factor, _lib.dptr(t2, "f64"),
+                     len(t2), self.stage2_factor, int(max_samples_per_call))
 
     def reset(self) -> None:
         _lib.check(_lib.lib.wh_ddc_reset(self._h), "wh_ddc_reset")
@@ -100,7 +91,7 @@ class TrunkingDDC:
         return self.process_device(self._torch.from_numpy(x).cuda(), offset_hz).cpu().numpy()
 
 
-class TrunkingDDCBank:
+class TrunkingDDCBank(_lib.Handle):
     """n_channels front-ends (NCO + two-stage decimator, each with its own offset, phase index and filter state)
     on one wideband buffer per call: the voice-recorder pool of trunking/system.py:453-656 plus the control
     monitor.  plan="recorder" uses VoiceRecorder.setup_decimation_filter's stage factors, plan="control" the
@@ -124,17 +115,8 @@ class TrunkingDDCBank:
         self.output_rate = self.sample_rate // self.stage1_factor // self.stage2_factor
         t1 = np.ascontiguousarray(self.stage1_taps, dtype=np.float64)
         t2 = np.ascontiguousarray(self.stage2_taps, dtype=np.float64)
-        self._h = C.c_void_p()
-        self._destroy = _lib.lib.wh_ddc_bank_destroy
-        _lib.check(_lib.lib.wh_ddc_bank_create(C.byref(self._h), self.n_channels, self.sample_rate, _lib.dptr(t1, "f64"),
-                                               len(t1), self.stage1_factor, _lib.dptr(t2, "f64"), len(t2),
-                                               self.stage2_factor, int(max_samples_per_call)), "wh_ddc_bank_create")
-
-    def __del__(self):
-        h, destroy = getattr(self, "_h", None), getattr(self, "_destroy", None)
-        if h and destroy:
-            destroy(h)
-            self._h = None
+        self._create("wh_ddc_bank", self.n_channels, self.sample_rate, _lib.dptr(t1, "f64"), len(t1), self.stage1_factor,
+                     _lib.dptr(t2, "f64"), len(t2), self.stage2_factor, int(max_samples_per_call))
 
     def reset(self, channel: int = -1) -> None:
         _lib.check(_lib.lib.wh_ddc_bank_reset(self._h, int(channel)), "wh_ddc_bank_reset")
