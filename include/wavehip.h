@@ -393,6 +393,35 @@ int wh_lsm_bank_reset(wh_lsm_bank *b, void *stream);
 int wh_lsm_bank_get_state(wh_lsm_bank *b, int channel, double *h_out, void *stream);
 void wh_lsm_bank_destroy(wh_lsm_bank *b);
 
+/* ---- Voice-recorder symbol path: FM discriminator (trunking/system.py:708-717) + DiscriminatorDemodulator
+ * (decoders/p25.py:1105-1345) for n_channels <= WH_DISC_MAX_CHANNELS independent channels.  Per call and channel:
+ * auto-gain (:1218-1227), per-sample DC tracker (:1229-1235), 'same'-mode baseband low-pass when n >= n_bb
+ * (:1237-1239), then _mmse_timing_recovery and the 4-level slicer (:1255-1333), in the reference's NumPy-2 scalar
+ * types.  h_bb_taps float32[n_bb] (firwin, :1201-1208; odd n_bb), h_mmse float32[129*8] (:1171-1192).
+ * run(): d_audio float32 [C][stride], n <= max_samples_per_call samples per channel = ONE demodulate() call.
+ * run_iq(): d_iq complex64 [C][stride] decimated IQ (wh_ddc_bank_run's output): float64 angle, np.unwrap against the
+ *   carried unwrapped last phase, np.diff -> float32 disc audio (written to d_disc [C][stride] when not NULL), which
+ *   feeds the demodulator in the same launch sequence.
+ * Both: h_active (optional) uint8[C], 0 = idle channel, state kept bit for bit; a row holding a non-finite sample
+ * leaves its channel's state untouched and yields 0 symbols (system.py:658-669, p25.py:2340-2342); d_dibits uint8
+ * [C][cap], cap >= n; d_counts int32 [C].  n == 0 is a no-op (counts 0).  reserve() grows the work buffers (state
+ * kept; synchronises).  reset(channel | -1, full): full = 0 is DiscriminatorDemodulator.reset() (input gain and
+ * carried phase kept), full = 1 a fresh recorder (new decoder, last phase 0).  get_state(): h_out[23] = symbol_clock,
+ * symbol_spread, dc_estimate, fine_freq, coarse_freq, input_gain, last_phase, the six "is float32" flags in that
+ * order, history_idx, symbol_count, history[8] (the reference's ring layout).                                      */
+#define WH_DISC_MAX_CHANNELS 1024
+typedef struct wh_disc_bank wh_disc_bank;
+int wh_disc_bank_create(wh_disc_bank **out, int n_channels, double sample_rate, double symbol_rate,
+                        const float *h_bb_taps, int n_bb, const float *h_mmse, size_t max_samples_per_call);
+int wh_disc_bank_run(wh_disc_bank *b, const float *d_audio, size_t n, size_t stride, const uint8_t *h_active,
+                     uint8_t *d_dibits, size_t cap, int32_t *d_counts, void *stream);
+int wh_disc_bank_run_iq(wh_disc_bank *b, const float *d_iq, size_t n, size_t stride, const uint8_t *h_active,
+                        float *d_disc, uint8_t *d_dibits, size_t cap, int32_t *d_counts, void *stream);
+int wh_disc_bank_reserve(wh_disc_bank *b, size_t max_samples_per_call, void *stream);
+int wh_disc_bank_reset(wh_disc_bank *b, int channel, int full, void *stream);
+int wh_disc_bank_get_state(wh_disc_bank *b, int channel, double *h_out, void *stream);
+void wh_disc_bank_destroy(wh_disc_bank *b);
+
 /* Gardner timing error detector bank, dsp/p25/symbol_timing.py:60-211 (GardnerTED.process_block):
  * d_x float32 [C][stride] -> d_symbols / d_errors float64 [C][cap], d_counts int32 [C].       */
 /* CostasLoop, dsp/p25/cqpsk.py:84-196, as a bank (standalone drop-in; the same loop runs fused inside wh_cqpsk_bank_run):

@@ -158,6 +158,16 @@ PROTOTYPES = {
     "wh_lsm_bank_reset": (c_int, [c_void_p, c_void_p]),
     "wh_lsm_bank_get_state": (c_int, [c_void_p, c_int, C.POINTER(c_double), c_void_p]),
     "wh_lsm_bank_destroy": (None, [c_void_p]),
+    "wh_disc_bank_create": (c_int, [C.POINTER(c_void_p), c_int, c_double, c_double, C.POINTER(c_float), c_int,
+                                    C.POINTER(c_float), c_size_t]),
+    "wh_disc_bank_run": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p,
+                                 c_void_p]),
+    "wh_disc_bank_run_iq": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t,
+                                    c_void_p, c_void_p]),
+    "wh_disc_bank_reserve": (c_int, [c_void_p, c_size_t, c_void_p]),
+    "wh_disc_bank_reset": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "wh_disc_bank_get_state": (c_int, [c_void_p, c_int, C.POINTER(c_double), c_void_p]),
+    "wh_disc_bank_destroy": (None, [c_void_p]),
     "wh_cqpsk_bank_create": (c_int, [C.POINTER(c_void_p), c_int, c_double, C.POINTER(c_float), c_int,
                                      C.POINTER(c_double), c_double, c_double, c_double, c_double, c_double, c_int]),
     "wh_cqpsk_bank_run": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p,
