@@ -6,7 +6,12 @@
  *   - every pointer named d_* is a DEVICE pointer (HBM) owned by the caller; every
  *     pointer named h_* is a host pointer read during the call only;
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream); calls only
- *     enqueue work, they never synchronise the device;
+ *     enqueue work, they never synchronise the device -- except when a workspace grows;
+ *   - growth (the *_reserve calls, and wh_chanbank_run / wh_pfb_run_stats when a call
+ *     is larger than any before): the new buffers are allocated first -- on failure the
+ *     call returns WH_E_HIP and the handle keeps its old buffers and capacity -- then
+ *     `stream` and the device are synchronised (earlier calls on any stream may still
+ *     use the old buffers) and the old buffers are freed.  A steady call size never grows;
  *   - return value: 0 = ok, <0 = WH_E_* ; wh_last_error() gives a thread-local text;
  *   - no global mutable state: handles may be used from different host threads as
  *     long as one handle is used by one thread at a time (the reference calls the
@@ -304,8 +309,8 @@ int wh_scan_measure(const float *d_iq, size_t n, int sample_rate, const int *h_o
  * not invariant to where a stream is cut: the whole call's symbols are extracted with the call-start equaliser, the
  * sync search runs on the 65 536-sample phase buffer as it stands after the call, symbols that were shifted out of
  * it carry index -1, c4fm.py:704-728, 2621-2770 -- production calls are 72 000-75 000 samples,
- * trunking/system.py:1548-1549).  n <= the bank's max_samples_per_call <= 2^24; reserve() grows that bound (it
- * allocates and synchronises -- not for the hot path), out_cap >= n / 4 + 2.                                   */
+ * trunking/system.py:1548-1549).  n <= the bank's max_samples_per_call <= 2^24; reserve() grows that bound (see
+ * "growth" above -- not for the hot path), out_cap >= n / 4 + 2.                                               */
 typedef struct wh_c4fm_bank wh_c4fm_bank;
 int wh_c4fm_bank_create(wh_c4fm_bank **out, int n_channels, double samples_per_symbol,
                         const float *h_lpf, int n_lpf, const float *h_rrc, int n_rrc,
@@ -355,7 +360,7 @@ void wh_bch_destroy(wh_bch *b);
  * NULL) complex128 [C][cap]; d_counts int32 [C].  State carried on the device.
  * ONE run() == ONE demodulate(iq) of the reference for any n <= max_samples_per_call (the reference re-seeds the
  * matched filter with zi = state * iq[0] on every call, cqpsk.py:283-285, so a stream cut differently gives different
- * dibits); reserve() grows max_samples_per_call (allocates and synchronises).  samples_per_symbol >= 2;
+ * dibits); reserve() grows max_samples_per_call (see "growth" above).  samples_per_symbol >= 2;
  * cap >= n / (samples_per_symbol / 2) + 2 (the timing loop's period never drops below sps / 2).              */
 typedef struct wh_cqpsk_bank wh_cqpsk_bank;
 int wh_cqpsk_bank_create(wh_cqpsk_bank **out, int n_channels, double samples_per_symbol, const float *h_rrc,
@@ -387,7 +392,7 @@ int wh_lsm_bank_create(wh_lsm_bank **out, int n_channels, double samples_per_sym
 int wh_lsm_bank_run(wh_lsm_bank *b, const float *d_iq, size_t n, size_t iq_stride, uint8_t *d_dibits, float *d_phases,
                     size_t cap, int32_t *d_counts, void *stream);
 /* grow the per-call work buffer so that calls of up to n_max samples are accepted (decoders/p25.py:413 takes any length);
- * carried state is untouched; synchronises the stream; no-op when n_max is not larger than what the bank already takes */
+ * carried state is untouched; see "growth" above; no-op when n_max is not larger than what the bank already takes */
 int wh_lsm_bank_reserve(wh_lsm_bank *b, int n_max, void *stream);
 int wh_lsm_bank_reset(wh_lsm_bank *b, void *stream);
 int wh_lsm_bank_get_state(wh_lsm_bank *b, int channel, double *h_out, void *stream);
@@ -405,7 +410,7 @@ void wh_lsm_bank_destroy(wh_lsm_bank *b);
  * Both: h_active (optional) uint8[C], 0 = idle channel, state kept bit for bit; a row holding a non-finite sample
  * leaves its channel's state untouched and yields 0 symbols (system.py:658-669, p25.py:2340-2342); d_dibits uint8
  * [C][cap], cap >= n; d_counts int32 [C].  n == 0 is a no-op (counts 0).  reserve() grows the work buffers (state
- * kept; synchronises).  reset(channel | -1, full): full = 0 is DiscriminatorDemodulator.reset() (input gain and
+ * kept; see "growth" above).  reset(channel | -1, full): full = 0 is DiscriminatorDemodulator.reset() (input gain and
  * carried phase kept), full = 1 a fresh recorder (new decoder, last phase 0).  get_state(): h_out[23] = symbol_clock,
  * symbol_spread, dc_estimate, fine_freq, coarse_freq, input_gain, last_phase, the six "is float32" flags in that
  * order, history_idx, symbol_count, history[8] (the reference's ring layout).                                      */

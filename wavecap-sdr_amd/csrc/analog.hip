@@ -1671,26 +1671,21 @@ extern "C" int wh_fm_discriminate(const float *d_iq, float *d_out, size_t n, int
 }
 
 struct wh_resampler {
-    double *d_taps = nullptr;
+    DevBuf<double> d_taps;
     int ntaps, up, down, d0;
 };
 
 extern "C" int wh_resampler_create(wh_resampler **out, const double *h_taps, int ntaps, int up, int down, int d0) {
     if (!out || !h_taps || ntaps < 1 || up < 1 || down < 1) return set_err(WH_E_ARG, "wh_resampler_create: bad args");
-    wh_resampler *r = new wh_resampler();
-    std::unique_ptr<wh_resampler, void (*)(wh_resampler *)> guard(r, wh_resampler_destroy);  // frees partial state on early return
+    std::unique_ptr<wh_resampler> r(new wh_resampler());   // frees partial state on early return
     r->ntaps = ntaps; r->up = up; r->down = down; r->d0 = d0;
-    WH_HIP(hipMalloc(&r->d_taps, (size_t)ntaps * sizeof(double)));
+    WH_HIP(r->d_taps.alloc((size_t)ntaps));
     WH_HIP(hipMemcpy(r->d_taps, h_taps, (size_t)ntaps * sizeof(double), hipMemcpyHostToDevice));
-    *out = guard.release();
+    *out = r.release();
     return WH_OK;
 }
 
-extern "C" void wh_resampler_destroy(wh_resampler *r) {
-    if (!r) return;
-    (void)hipFree(r->d_taps);
-    delete r;
-}
+extern "C" void wh_resampler_destroy(wh_resampler *r) { delete r; }
 
 static int launch_resample(const float *d_x, size_t n_in, size_t x_stride, size_t batch, float *d_y, size_t n_out,
                            const double *taps, int ntaps, int up, int down, int d0, hipStream_t st) {
@@ -1870,33 +1865,33 @@ static void rows_shape(const wh_chanbank_cfg &c, bool fir_start, int *rw_out, in
 
 struct wh_chanbank {
     wh_chanbank_cfg cfg;
-    float *d_nco = nullptr;
-    float *d_squelch = nullptr;
+    DevBuf<float> d_nco;
+    DevBuf<float> d_squelch;
     std::vector<float> h_stage[2];   // host side of wh_chanbank_set_offsets / _set_squelch (alternating, kept alive)
     int h_stage_cur = 0;
-    double *d_taps = nullptr;
+    DevBuf<double> d_taps;
     StageArr stages{};
-    ScanPow *d_pow = nullptr;   // scan form: per-stage state-transition powers for the bank's segment length
+    DevBuf<ScanPow> d_pow;   // scan form: per-stage state-transition powers for the bank's segment length
     int scan_seg = 0, scan_w = 1;   // scan form: segment length, waves per row (64 segments each)
-    double *d_G = nullptr;          // warm-up form: impulse-response states [iir_warmup][start_ep]
-    double *d_S0 = nullptr;         // ... and the segments' start states of a call [rows][segments][start_ep]
+    DevBuf<double> d_G;             // warm-up form: impulse-response states [iir_warmup][start_ep]
+    DevBuf<double> d_S0;            // ... and the segments' start states of a call [rows][segments][start_ep]
     int start_ep = 0;               // row length of d_G / d_S0: the chain's state count rounded up to even
-    double *d_acc = nullptr;
-    float *d_fm = nullptr;
-    float *d_araw = nullptr;   // fused FM path: raw discriminator angles of the call's chunks [n_chunks][N]
+    DevBuf<double> d_acc;
+    DevBuf<float> d_fm;
+    DevBuf<float> d_araw;   // fused FM path: raw discriminator angles of the call's chunks [n_chunks][N]
     size_t cap_chunks = 0;
     bool fused = false;
     bool rows_fir = false;   // unfused chain whose resampler is the fused kernel's decimating FIR
     int fir_phase = 0;       // the FIR's polyphase register form (see fm_fir_phases)
-    float2 *d_tphase = nullptr;
+    DevBuf<float2> d_tphase;
     int TO = 128;
     size_t smem = 0;
     int post = 0;
     // spectral noise reduction workspace
     bool nr = false;
     int nr_frames = 0, nr_len = 0;
-    float *d_nr_win = nullptr, *d_nr_mag = nullptr, *d_nr_sel = nullptr;
-    float2 *d_nr_tw = nullptr, *d_nr_stft = nullptr;
+    DevBuf<float> d_nr_win, d_nr_mag, d_nr_sel;
+    DevBuf<float2> d_nr_tw, d_nr_stft;
 };
 
 // Retune without rebuilding the bank (API PATCH of offset_hz -> capture.py:442-501): the mixer constant is one float32
@@ -1935,8 +1930,7 @@ extern "C" int wh_chanbank_create(wh_chanbank **out, const wh_chanbank_cfg *c) {
     for (int i = 0; i < c->n_stages; ++i)
         if (c->h_stages[i].n < 1 || c->h_stages[i].n > MAX_ORD || c->h_stages[i].a[0] == 0.0)
             return set_err(WH_E_ARG, "wh_chanbank_create: bad IIR stage %d", i);
-    wh_chanbank *b = new wh_chanbank();
-    std::unique_ptr<wh_chanbank, void (*)(wh_chanbank *)> guard(b, wh_chanbank_destroy);  // frees partial state on early return
+    std::unique_ptr<wh_chanbank> b(new wh_chanbank());   // frees partial state on early return
     b->cfg = *c;
     b->cfg.h_offsets_hz = nullptr;
     b->cfg.h_taps = nullptr;
@@ -1954,8 +1948,8 @@ extern "C" int wh_chanbank_create(wh_chanbank **out, const wh_chanbank_cfg *c) {
                 double ang = -2.0 * M_PI * (double)m / (double)NR_FFT;
                 tw[m] = make_float2((float)cos(ang), (float)sin(ang));
             }
-            WH_HIP(hipMalloc(&b->d_nr_win, NR_FFT * sizeof(float)));
-            WH_HIP(hipMalloc(&b->d_nr_tw, NR_FFT * sizeof(float2)));
+            WH_HIP(b->d_nr_win.alloc(NR_FFT));
+            WH_HIP(b->d_nr_tw.alloc(NR_FFT));
             WH_HIP(hipMemcpy(b->d_nr_win, c->h_nr_window, NR_FFT * sizeof(float), hipMemcpyHostToDevice));
             WH_HIP(hipMemcpy(b->d_nr_tw, tw.data(), NR_FFT * sizeof(float2), hipMemcpyHostToDevice));
         }
@@ -1969,15 +1963,15 @@ extern "C" int wh_chanbank_create(wh_chanbank **out, const wh_chanbank_cfg *c) {
     }
     std::vector<float> nco(c->n_channels);
     for (int k = 0; k < c->n_channels; ++k) nco[k] = c->h_offsets_hz[k] == 0 ? 0.0f : nco_const(c->h_offsets_hz[k], c->sample_rate);
-    WH_HIP(hipMalloc(&b->d_nco, nco.size() * sizeof(float)));
+    WH_HIP(b->d_nco.alloc(nco.size()));
     WH_HIP(hipMemcpy(b->d_nco, nco.data(), nco.size() * sizeof(float), hipMemcpyHostToDevice));
     if (c->h_squelch_db) {
-        WH_HIP(hipMalloc(&b->d_squelch, (size_t)c->n_channels * sizeof(float)));
+        WH_HIP(b->d_squelch.alloc((size_t)c->n_channels));
         WH_HIP(hipMemcpy(b->d_squelch, c->h_squelch_db, (size_t)c->n_channels * sizeof(float), hipMemcpyHostToDevice));
     }
     b->cfg.h_squelch_db = nullptr;
     if (resample) {
-        WH_HIP(hipMalloc(&b->d_taps, (size_t)c->ntaps * sizeof(double)));
+        WH_HIP(b->d_taps.alloc((size_t)c->ntaps));
         WH_HIP(hipMemcpy(b->d_taps, c->h_taps, (size_t)c->ntaps * sizeof(double), hipMemcpyHostToDevice));
     }
     if (c->n_stages > 0) {
@@ -2021,7 +2015,7 @@ extern "C" int wh_chanbank_create(wh_chanbank **out, const wh_chanbank_cfg *c) {
             g.on = c->agc; g.target = c->agc_target; g.max_gain = c->agc_max_gain;
             g.att_b0 = c->agc_att_b0; g.att_a1 = c->agc_att_a1; g.rel_b0 = c->agc_rel_b0; g.rel_a1 = c->agc_rel_a1;
             // transition powers over one segment and over a wave's 64 segments
-            WH_HIP(hipMalloc(&b->d_pow, 2 * sizeof(ScanPow)));
+            WH_HIP(b->d_pow.alloc(2));
             WH_HIP(hipMemset(b->d_pow, 0, 2 * sizeof(ScanPow)));
             hipLaunchKernelGGL(iir_pow_kernel, dim3(c->n_stages + 1), dim3(MAX_ORD - 1), 0, nullptr, b->stages, c->n_stages, g,
                                sg, b->d_pow);
@@ -2046,7 +2040,7 @@ extern "C" int wh_chanbank_create(wh_chanbank **out, const wh_chanbank_cfg *c) {
         const int EP = (E + 1) & ~1;
         if (E >= 1 && EP <= 16 && c->n_stages <= 3) {   // (longer state vectors keep the recurrence warm-up)
             b->start_ep = EP;
-            WH_HIP(hipMalloc(&b->d_G, (size_t)c->iir_warmup * EP * sizeof(double)));
+            WH_HIP(b->d_G.alloc((size_t)c->iir_warmup * EP));
             hipLaunchKernelGGL(iir_impulse_kernel, dim3(1), dim3(1), 0, nullptr, b->stages, c->n_stages, c->iir_warmup, EP,
                                b->d_G);
             WH_LAUNCH_CHECK();
@@ -2088,7 +2082,7 @@ extern "C" int wh_chanbank_create(wh_chanbank **out, const wh_chanbank_cfg *c) {
                     tp[(size_t)q * 32 + rp] = make_float2(i < c->ntaps ? (float)c->h_taps[c->ntaps - 1 - i] : 0.f,
                                                           i + 1 < c->ntaps ? (float)c->h_taps[c->ntaps - 2 - i] : 0.f);
                 }
-            WH_HIP(hipMalloc(&b->d_tphase, tp.size() * sizeof(float2)));
+            WH_HIP(b->d_tphase.alloc(tp.size()));
             WH_HIP(hipMemcpy(b->d_tphase, tp.data(), tp.size() * sizeof(float2), hipMemcpyHostToDevice));
         }
         if (c->ntaps + (TO - 1) * c->down <= FM_MAX_SPAN) {
@@ -2103,26 +2097,11 @@ extern "C" int wh_chanbank_create(wh_chanbank **out, const wh_chanbank_cfg *c) {
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->smem));
         }
     }
-    *out = guard.release();
+    *out = b.release();
     return WH_OK;
 }
 
-extern "C" void wh_chanbank_destroy(wh_chanbank *b) {
-    if (!b) return;
-    (void)hipFree(b->d_nco);
-    (void)hipFree(b->d_tphase);
-    (void)hipFree(b->d_squelch);
-    (void)hipFree(b->d_pow);
-    (void)hipFree(b->d_G);
-    (void)hipFree(b->d_S0);
-    (void)hipFree(b->d_taps);
-    (void)hipFree(b->d_acc);
-    (void)hipFree(b->d_fm);
-    (void)hipFree(b->d_araw);
-    (void)hipFree(b->d_nr_win); (void)hipFree(b->d_nr_tw); (void)hipFree(b->d_nr_mag); (void)hipFree(b->d_nr_sel);
-    (void)hipFree(b->d_nr_stft);
-    delete b;
-}
+extern "C" void wh_chanbank_destroy(wh_chanbank *b) { delete b; }
 
 extern "C" size_t wh_chanbank_workspace_bytes(const wh_chanbank *b, size_t n_chunks) {
     if (!b) return 0;
@@ -2151,32 +2130,26 @@ extern "C" int wh_chanbank_run_wire(wh_chanbank *b, const void *d_in, size_t n_c
     const size_t rows = n_chunks * (size_t)c.n_channels;
     const bool resample = c.ntaps > 0;
     if (n_chunks > b->cap_chunks) {  // grow the workspace (synchronises; steady state never does)
-        WH_HIP(hipStreamSynchronize(st));
-        (void)hipFree(b->d_acc);
-        (void)hipFree(b->d_fm);
-        (void)hipFree(b->d_araw);
-        b->d_acc = nullptr;
-        b->d_fm = nullptr;
-        b->d_araw = nullptr;
-        WH_HIP(hipMalloc(&b->d_acc, rows * 2 * sizeof(double)));
-        if (b->fused) WH_HIP(hipMalloc(&b->d_araw, n_chunks * (size_t)c.chunk_len * sizeof(float)));
-        if (!b->fused && (resample || b->nr)) WH_HIP(hipMalloc(&b->d_fm, rows * (size_t)c.chunk_len * sizeof(float)));
+        DevBuf<double> acc, S0;
+        DevBuf<float> araw, fm, nr_mag, nr_sel;
+        DevBuf<float2> nr_stft;
+        WH_HIP(acc.alloc(rows * 2));
+        if (b->fused) WH_HIP(araw.alloc(n_chunks * (size_t)c.chunk_len));
+        if (!b->fused && (resample || b->nr)) WH_HIP(fm.alloc(rows * (size_t)c.chunk_len));
         if (b->d_G) {
-            (void)hipFree(b->d_S0);
-            b->d_S0 = nullptr;
             // (segments per row: the warm-up form's wave count is a property of the bank, see below)
             int rw, rg;
-            rows_shape(c, b->d_G != nullptr, &rw, &rg);
-            WH_HIP(hipMalloc(&b->d_S0, rows * (size_t)(64 * rw * rg) * b->start_ep * sizeof(double)));
+            rows_shape(c, true, &rw, &rg);
+            WH_HIP(S0.alloc(rows * (size_t)(64 * rw * rg) * b->start_ep));
         }
         if (b->nr) {
-            (void)hipFree(b->d_nr_mag); (void)hipFree(b->d_nr_sel); (void)hipFree(b->d_nr_stft);
-            b->d_nr_mag = b->d_nr_sel = nullptr;
-            b->d_nr_stft = nullptr;
-            WH_HIP(hipMalloc(&b->d_nr_stft, rows * (size_t)b->nr_frames * NR_BINS * sizeof(float2)));
-            WH_HIP(hipMalloc(&b->d_nr_mag, rows * (size_t)b->nr_frames * NR_BINS * sizeof(float)));
-            WH_HIP(hipMalloc(&b->d_nr_sel, rows * (size_t)NR_BINS * 2 * sizeof(float)));
+            WH_HIP(nr_stft.alloc(rows * (size_t)b->nr_frames * NR_BINS));
+            WH_HIP(nr_mag.alloc(rows * (size_t)b->nr_frames * NR_BINS));
+            WH_HIP(nr_sel.alloc(rows * (size_t)NR_BINS * 2));
         }
+        WH_HIP(sync_before_swap(st));
+        b->d_acc = std::move(acc); b->d_araw = std::move(araw); b->d_fm = std::move(fm); b->d_S0 = std::move(S0);
+        b->d_nr_stft = std::move(nr_stft); b->d_nr_mag = std::move(nr_mag); b->d_nr_sel = std::move(nr_sel);
         b->cap_chunks = n_chunks;
     }
     WH_HIP(hipMemsetAsync(b->d_acc, 0, rows * 2 * sizeof(double), st));

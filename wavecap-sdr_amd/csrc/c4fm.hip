@@ -626,14 +626,14 @@ constexpr size_t C4_LDS_STREAMS = 64 * 1024;  // detector streams beyond this ma
 struct wh_c4fm_bank {
     int C, n_max = 0, nl, nr, overlap, interp_offset, fm_row, ns_max = 0;
     double sps;
-    float *d_lpf = nullptr, *d_rrc = nullptr, *d_taps = nullptr;
-    float2 *d_xh = nullptr;
-    double2 *d_y = nullptr;
-    float2 *d_z = nullptr;
-    float *d_phases = nullptr, *d_buffer = nullptr, *d_ss = nullptr;
-    ChanState *d_st = nullptr;
-    int *d_sym_x = nullptr, *d_sym_idx = nullptr;
-    double *d_sym_sp = nullptr;
+    DevBuf<float> d_lpf, d_rrc, d_taps;
+    DevBuf<float2> d_xh;
+    DevBuf<double2> d_y;
+    DevBuf<float2> d_z;
+    DevBuf<float> d_phases, d_buffer, d_ss;
+    DevBuf<ChanState> d_st;
+    DevBuf<int> d_sym_x, d_sym_idx;
+    DevBuf<double> d_sym_sp;
 };
 
 static int c4_ns(double sps, int n) { return (int)((double)n / sps) + 16; }
@@ -644,44 +644,35 @@ static size_t c4_stream_bytes(int ns) { return (size_t)2 * (24 + ns) * sizeof(fl
 static int c4fm_resize(wh_c4fm_bank *b, int n_max, hipStream_t st) {
     const int C = b->C, Hy = b->nr - 1, Hz = b->overlap;
     const int ns_max = c4_ns(b->sps, n_max);
-    double2 *y = nullptr;
-    float2 *z = nullptr;
-    float *ph = nullptr, *ss = nullptr;
-    int *sx = nullptr, *si = nullptr;
-    double *sp = nullptr;
-    auto drop = [&]() {
-        (void)hipFree(y); (void)hipFree(z); (void)hipFree(ph); (void)hipFree(ss); (void)hipFree(sx); (void)hipFree(si);
-        (void)hipFree(sp);
-    };
-#define C4_TRY(x)                                                                                  \
-    do {                                                                                           \
-        hipError_t e_ = (x);                                                                       \
-        if (e_ != hipSuccess) { drop(); return set_err(WH_E_HIP, "c4fm workspace: %s", hipGetErrorString(e_)); }       \
-    } while (0)
-    C4_TRY(hipMalloc(&y, (size_t)C * (Hy + n_max) * sizeof(double2)));
-    C4_TRY(hipMalloc(&z, (size_t)C * (Hz + n_max) * sizeof(float2)));
-    C4_TRY(hipMalloc(&ph, (size_t)C * n_max * sizeof(float)));
-    C4_TRY(hipMalloc(&sx, (size_t)C * ns_max * sizeof(int)));
-    C4_TRY(hipMalloc(&si, (size_t)C * ns_max * sizeof(int)));
-    C4_TRY(hipMalloc(&sp, (size_t)C * ns_max * sizeof(double)));
-    if (c4_stream_bytes(ns_max) > C4_LDS_STREAMS) C4_TRY(hipMalloc(&ss, (size_t)C * c4_stream_bytes(ns_max)));
-    if (b->d_y) {
-        C4_TRY(hipMemcpy2DAsync(y, (size_t)(Hy + n_max) * sizeof(double2), b->d_y,
-                                (size_t)(Hy + b->n_max) * sizeof(double2), (size_t)Hy * sizeof(double2), C,
-                                hipMemcpyDeviceToDevice, st));
-        C4_TRY(hipMemcpy2DAsync(z, (size_t)(Hz + n_max) * sizeof(float2), b->d_z,
-                                (size_t)(Hz + b->n_max) * sizeof(float2), (size_t)Hz * sizeof(float2), C,
-                                hipMemcpyDeviceToDevice, st));
+    DevBuf<double2> y;
+    DevBuf<float2> z;
+    DevBuf<float> ph, ss;
+    DevBuf<int> sx, si;
+    DevBuf<double> sp;
+    hipError_t e = y.alloc((size_t)C * (Hy + n_max));
+    if (e == hipSuccess) e = z.alloc((size_t)C * (Hz + n_max));
+    if (e == hipSuccess) e = ph.alloc((size_t)C * n_max);
+    if (e == hipSuccess) e = sx.alloc((size_t)C * ns_max);
+    if (e == hipSuccess) e = si.alloc((size_t)C * ns_max);
+    if (e == hipSuccess) e = sp.alloc((size_t)C * ns_max);
+    if (e == hipSuccess && c4_stream_bytes(ns_max) > C4_LDS_STREAMS)
+        e = ss.alloc((size_t)C * c4_stream_bytes(ns_max) / sizeof(float));
+    if (e != hipSuccess) return set_err(WH_E_HIP, "c4fm workspace: %s", hipGetErrorString(e));
+    if (b->d_y) {   // carry the FIR heads
+        e = hipMemcpy2DAsync(y, (size_t)(Hy + n_max) * sizeof(double2), b->d_y, (size_t)(Hy + b->n_max) * sizeof(double2),
+                             (size_t)Hy * sizeof(double2), C, hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess)
+            e = hipMemcpy2DAsync(z, (size_t)(Hz + n_max) * sizeof(float2), b->d_z,
+                                 (size_t)(Hz + b->n_max) * sizeof(float2), (size_t)Hz * sizeof(float2), C,
+                                 hipMemcpyDeviceToDevice, st);
     } else {
-        C4_TRY(hipMemsetAsync(y, 0, (size_t)C * (Hy + n_max) * sizeof(double2), st));
-        C4_TRY(hipMemsetAsync(z, 0, (size_t)C * (Hz + n_max) * sizeof(float2), st));
+        e = hipMemsetAsync(y, 0, (size_t)C * (Hy + n_max) * sizeof(double2), st);
+        if (e == hipSuccess) e = hipMemsetAsync(z, 0, (size_t)C * (Hz + n_max) * sizeof(float2), st);
     }
-    C4_TRY(hipStreamSynchronize(st));   // the copies above
-    C4_TRY(hipDeviceSynchronize());     // earlier calls (on whichever stream) may still use the old workspaces
-#undef C4_TRY
-    (void)hipFree(b->d_y); (void)hipFree(b->d_z); (void)hipFree(b->d_phases); (void)hipFree(b->d_ss);
-    (void)hipFree(b->d_sym_x); (void)hipFree(b->d_sym_idx); (void)hipFree(b->d_sym_sp);
-    b->d_y = y; b->d_z = z; b->d_phases = ph; b->d_ss = ss; b->d_sym_x = sx; b->d_sym_idx = si; b->d_sym_sp = sp;
+    if (e == hipSuccess) e = sync_before_swap(st);
+    if (e != hipSuccess) return set_err(WH_E_HIP, "c4fm workspace: %s", hipGetErrorString(e));
+    b->d_y = std::move(y); b->d_z = std::move(z); b->d_phases = std::move(ph); b->d_ss = std::move(ss);
+    b->d_sym_x = std::move(sx); b->d_sym_idx = std::move(si); b->d_sym_sp = std::move(sp);
     b->n_max = n_max; b->ns_max = ns_max;
     return WH_OK;
 }
@@ -702,8 +693,7 @@ extern "C" int wh_c4fm_bank_create(wh_c4fm_bank **out, int C, double sps, const 
     if (C < 1 || nl < 2 || nr < 2 || nl > 1024 || nr > 2048 || !(sps >= 4.0) || sps > 512.0 || n_max < 1 ||
         n_max > C4_N_CAP)
         return set_err(WH_E_ARG, "wh_c4fm_bank_create: need sps >= 4, 1 <= max_samples_per_call <= 2^24");
-    wh_c4fm_bank *b = new wh_c4fm_bank();
-    std::unique_ptr<wh_c4fm_bank, void (*)(wh_c4fm_bank *)> guard(b, wh_c4fm_bank_destroy);  // frees partial state on early return
+    std::unique_ptr<wh_c4fm_bank> b(new wh_c4fm_bank());   // frees partial state on early return
     b->C = C; b->nl = nl; b->nr = nr; b->sps = sps;
     int fl = (int)floor(sps);
     b->interp_offset = fl - 4 > 0 ? fl - 4 : 0;
@@ -711,21 +701,21 @@ extern "C" int wh_c4fm_bank_create(wh_c4fm_bank **out, int C, double sps, const 
     double mu = fmod(sps, 1.0);
     int row = (int)((1.0 - mu) * 128.0 + 0.5);
     b->fm_row = row < 0 ? 0 : (row > 128 ? 128 : row);
-    WH_HIP(hipMalloc(&b->d_lpf, nl * sizeof(float)));
-    WH_HIP(hipMalloc(&b->d_rrc, nr * sizeof(float)));
-    WH_HIP(hipMalloc(&b->d_taps, 129 * 8 * sizeof(float)));
+    WH_HIP(b->d_lpf.alloc(nl));
+    WH_HIP(b->d_rrc.alloc(nr));
+    WH_HIP(b->d_taps.alloc(129 * 8));
     WH_HIP(hipMemcpy(b->d_lpf, h_lpf, nl * sizeof(float), hipMemcpyHostToDevice));
     WH_HIP(hipMemcpy(b->d_rrc, h_rrc, nr * sizeof(float), hipMemcpyHostToDevice));
     WH_HIP(hipMemcpy(b->d_taps, h_taps, 129 * 8 * sizeof(float), hipMemcpyHostToDevice));
-    WH_HIP(hipMalloc(&b->d_xh, (size_t)C * (nl - 1) * sizeof(float2)));
-    WH_HIP(hipMalloc(&b->d_buffer, (size_t)C * BUF_LEN * sizeof(float)));
-    WH_HIP(hipMalloc(&b->d_st, (size_t)C * sizeof(ChanState)));
-    int rc = c4fm_resize(b, n_max, nullptr);
+    WH_HIP(b->d_xh.alloc((size_t)C * (nl - 1)));
+    WH_HIP(b->d_buffer.alloc((size_t)C * BUF_LEN));
+    WH_HIP(b->d_st.alloc((size_t)C));
+    int rc = c4fm_resize(b.get(), n_max, nullptr);
     if (rc != WH_OK) return rc;
-    rc = c4fm_zero_state(b, nullptr);
+    rc = c4fm_zero_state(b.get(), nullptr);
     if (rc != WH_OK) return rc;
     WH_HIP(hipDeviceSynchronize());
-    *out = guard.release();
+    *out = b.release();
     return WH_OK;
 }
 
@@ -738,14 +728,7 @@ extern "C" int wh_c4fm_bank_reserve(wh_c4fm_bank *b, size_t n_max, void *stream)
     return c4fm_resize(b, (int)n_max, as_stream(stream));
 }
 
-extern "C" void wh_c4fm_bank_destroy(wh_c4fm_bank *b) {
-    if (!b) return;
-    (void)hipFree(b->d_lpf); (void)hipFree(b->d_rrc); (void)hipFree(b->d_taps); (void)hipFree(b->d_xh);
-    (void)hipFree(b->d_y); (void)hipFree(b->d_z); (void)hipFree(b->d_phases); (void)hipFree(b->d_buffer);
-    (void)hipFree(b->d_ss);
-    (void)hipFree(b->d_st); (void)hipFree(b->d_sym_x); (void)hipFree(b->d_sym_idx); (void)hipFree(b->d_sym_sp);
-    delete b;
-}
+extern "C" void wh_c4fm_bank_destroy(wh_c4fm_bank *b) { delete b; }
 
 extern "C" int wh_c4fm_bank_reset(wh_c4fm_bank *b, void *stream) {
     if (!b) return set_err(WH_E_ARG, "wh_c4fm_bank_reset: null handle");

@@ -489,10 +489,10 @@ struct wh_cqpsk_bank {
     int C, n_max, L;
     double sps, c_kp, c_ki, c_maxf, t_kp, t_ki;
     std::vector<double> zi0;
-    double *d_taps = nullptr;
-    double2 *d_state[2] = {nullptr, nullptr}, *d_full = nullptr, *d_symws = nullptr;
+    DevBuf<double> d_taps;
+    DevBuf<double2> d_state[2], d_full, d_symws;
     size_t symcap = 0;
-    CqState *d_st = nullptr;
+    DevBuf<CqState> d_st;
     int cur = 0;
 };
 
@@ -513,55 +513,42 @@ extern "C" int wh_cqpsk_bank_create(wh_cqpsk_bank **out, int C, double sps, cons
                                     double t_ki, int n_max) {
     if (!out || !h_rrc || !h_zi || C < 1 || ntaps < 2 || ntaps > 4096 || !(sps >= 2.0) || n_max < 1)
         return set_err(WH_E_ARG, "wh_cqpsk_bank_create: bad arguments (samples_per_symbol >= 2)");
-    wh_cqpsk_bank *b = new wh_cqpsk_bank();
-    std::unique_ptr<wh_cqpsk_bank, void (*)(wh_cqpsk_bank *)> guard(b, wh_cqpsk_bank_destroy);  // frees partial state on early return
+    std::unique_ptr<wh_cqpsk_bank> b(new wh_cqpsk_bank());   // frees partial state on early return
     b->C = C; b->n_max = n_max; b->L = ntaps; b->sps = sps;
     b->c_kp = c_kp; b->c_ki = c_ki; b->c_maxf = c_maxf; b->t_kp = t_kp; b->t_ki = t_ki;
     b->zi0.assign(h_zi, h_zi + ntaps - 1);
     std::vector<double> taps(ntaps);
     for (int i = 0; i < ntaps; ++i) taps[i] = (double)h_rrc[i];
     const int H = ntaps - 1;
-    WH_HIP(hipMalloc(&b->d_taps, ntaps * sizeof(double)));
+    WH_HIP(b->d_taps.alloc(ntaps));
     WH_HIP(hipMemcpy(b->d_taps, taps.data(), ntaps * sizeof(double), hipMemcpyHostToDevice));
-    for (int i = 0; i < 2; ++i) WH_HIP(hipMalloc(&b->d_state[i], (size_t)C * H * sizeof(double2)));
-    WH_HIP(hipMalloc(&b->d_full, (size_t)C * (n_max + H) * sizeof(double2)));
+    for (int i = 0; i < 2; ++i) WH_HIP(b->d_state[i].alloc((size_t)C * H));
+    WH_HIP(b->d_full.alloc((size_t)C * (n_max + H)));
     b->symcap = mm_symbol_bound((size_t)n_max, sps);
-    WH_HIP(hipMalloc(&b->d_symws, (size_t)C * b->symcap * sizeof(double2)));
-    WH_HIP(hipMalloc(&b->d_st, (size_t)C * sizeof(CqState)));
-    int rc = cq_reset(b, nullptr);
+    WH_HIP(b->d_symws.alloc((size_t)C * b->symcap));
+    WH_HIP(b->d_st.alloc((size_t)C));
+    int rc = cq_reset(b.get(), nullptr);
     if (rc != WH_OK) return rc;
-    *out = guard.release();
+    *out = b.release();
     return WH_OK;
 }
 
-extern "C" void wh_cqpsk_bank_destroy(wh_cqpsk_bank *b) {
-    if (!b) return;
-    (void)hipFree(b->d_taps); (void)hipFree(b->d_state[0]); (void)hipFree(b->d_state[1]); (void)hipFree(b->d_full);
-    (void)hipFree(b->d_symws);
-    (void)hipFree(b->d_st);
-    delete b;
-}
-
-// symbols a call of n samples can produce: the Mueller-Muller period is clamped to [sps / 2, ...] (integrator within
-// +-sps / 4, symbol_timing.py:330-345), bound computed in floating point (sps / 2 need not be an integer)
+extern "C" void wh_cqpsk_bank_destroy(wh_cqpsk_bank *b) { delete b; }
 
 // Grow the matched-filter workspace for calls of up to n_max samples per channel (never shrinks; no state lives in it).
-// Allocates and synchronises the stream: not for the hot path.
+// Allocates and synchronises the stream and the device: not for the hot path.
 extern "C" int wh_cqpsk_bank_reserve(wh_cqpsk_bank *b, size_t n_max, void *stream) {
     if (!b) return set_err(WH_E_ARG, "wh_cqpsk_bank_reserve: null handle");
     if (n_max > (size_t)1 << 26) return set_err(WH_E_ARG, "wh_cqpsk_bank_reserve: more than 2^26 samples per call");
     if (n_max <= (size_t)b->n_max) return WH_OK;
-    double2 *full = nullptr, *symws = nullptr;
     const size_t symcap = mm_symbol_bound(n_max, b->sps);
-    WH_HIP(hipMalloc(&full, (size_t)b->C * (n_max + b->L - 1) * sizeof(double2)));
-    hipError_t e = hipMalloc(&symws, (size_t)b->C * symcap * sizeof(double2));
-    (void)stream;
-    if (e == hipSuccess) e = hipDeviceSynchronize();   // earlier calls (on whichever stream) may still read the old workspaces
-    if (e != hipSuccess) { (void)hipFree(full); (void)hipFree(symws); return set_err(WH_E_HIP, "wh_cqpsk_bank_reserve: %s", hipGetErrorString(e)); }
-    (void)hipFree(b->d_full);
-    (void)hipFree(b->d_symws);
-    b->d_full = full;
-    b->d_symws = symws;
+    DevBuf<double2> full, symws;
+    WH_HIP(full.alloc((size_t)b->C * (n_max + b->L - 1)));
+    hipError_t e = symws.alloc((size_t)b->C * symcap);
+    if (e == hipSuccess) e = sync_before_swap(as_stream(stream));
+    if (e != hipSuccess) return set_err(WH_E_HIP, "wh_cqpsk_bank_reserve: %s", hipGetErrorString(e));
+    b->d_full = std::move(full);
+    b->d_symws = std::move(symws);
     b->symcap = symcap;
     b->n_max = (int)n_max;
     return WH_OK;
@@ -613,25 +600,20 @@ extern "C" int wh_cqpsk_bank_run(wh_cqpsk_bank *b, const float *d_iq, size_t n, 
 struct wh_gardner_bank {
     int C;
     double sps, kp, ki;
-    GState *d_st = nullptr;
+    DevBuf<GState> d_st;
 };
 
 extern "C" int wh_gardner_bank_create(wh_gardner_bank **out, int C, double sps, double kp, double ki) {
     if (!out || C < 1 || !(sps > 1.0)) return set_err(WH_E_ARG, "wh_gardner_bank_create: bad arguments");
-    wh_gardner_bank *g = new wh_gardner_bank();
-    std::unique_ptr<wh_gardner_bank, void (*)(wh_gardner_bank *)> guard(g, wh_gardner_bank_destroy);  // frees partial state on early return
+    std::unique_ptr<wh_gardner_bank> g(new wh_gardner_bank());   // frees partial state on early return
     g->C = C; g->sps = sps; g->kp = kp; g->ki = ki;
-    WH_HIP(hipMalloc(&g->d_st, (size_t)C * sizeof(GState)));
+    WH_HIP(g->d_st.alloc((size_t)C));
     WH_HIP(hipMemset(g->d_st, 0, (size_t)C * sizeof(GState)));
-    *out = guard.release();
+    *out = g.release();
     return WH_OK;
 }
 
-extern "C" void wh_gardner_bank_destroy(wh_gardner_bank *g) {
-    if (!g) return;
-    (void)hipFree(g->d_st);
-    delete g;
-}
+extern "C" void wh_gardner_bank_destroy(wh_gardner_bank *g) { delete g; }
 
 extern "C" int wh_gardner_bank_reset(wh_gardner_bank *g, void *stream) {
     if (!g) return set_err(WH_E_ARG, "wh_gardner_bank_reset: null handle");
@@ -659,25 +641,20 @@ extern "C" int wh_gardner_bank_run(wh_gardner_bank *g, const float *d_x, size_t 
 struct wh_costas_bank {
     int C;
     double kp, ki, maxf;
-    CostasState *d_st = nullptr;
+    DevBuf<CostasState> d_st;
 };
 
 extern "C" int wh_costas_bank_create(wh_costas_bank **out, int C, double kp, double ki, double max_freq) {
     if (!out || C < 1 || !(max_freq >= 0.0)) return set_err(WH_E_ARG, "wh_costas_bank_create: bad arguments");
-    wh_costas_bank *b = new wh_costas_bank();
-    std::unique_ptr<wh_costas_bank, void (*)(wh_costas_bank *)> guard(b, wh_costas_bank_destroy);
+    std::unique_ptr<wh_costas_bank> b(new wh_costas_bank());
     b->C = C; b->kp = kp; b->ki = ki; b->maxf = max_freq;
-    WH_HIP(hipMalloc(&b->d_st, (size_t)C * sizeof(CostasState)));
+    WH_HIP(b->d_st.alloc((size_t)C));
     WH_HIP(hipMemset(b->d_st, 0, (size_t)C * sizeof(CostasState)));
-    *out = guard.release();
+    *out = b.release();
     return WH_OK;
 }
 
-extern "C" void wh_costas_bank_destroy(wh_costas_bank *b) {
-    if (!b) return;
-    (void)hipFree(b->d_st);
-    delete b;
-}
+extern "C" void wh_costas_bank_destroy(wh_costas_bank *b) { delete b; }
 
 extern "C" int wh_costas_bank_reset(wh_costas_bank *b, void *stream) {
     if (!b) return set_err(WH_E_ARG, "wh_costas_bank_reset: null handle");
@@ -707,25 +684,20 @@ extern "C" int wh_costas_bank_run(wh_costas_bank *b, const double *d_x, size_t n
 struct wh_mm_bank {
     int C;
     double sps, kp, ki;
-    MmState *d_st = nullptr;
+    DevBuf<MmState> d_st;
 };
 
 extern "C" int wh_mm_bank_create(wh_mm_bank **out, int C, double sps, double kp, double ki) {
     if (!out || C < 1 || !(sps >= 2.0)) return set_err(WH_E_ARG, "wh_mm_bank_create: bad arguments (samples_per_symbol >= 2)");
-    wh_mm_bank *b = new wh_mm_bank();
-    std::unique_ptr<wh_mm_bank, void (*)(wh_mm_bank *)> guard(b, wh_mm_bank_destroy);
+    std::unique_ptr<wh_mm_bank> b(new wh_mm_bank());
     b->C = C; b->sps = sps; b->kp = kp; b->ki = ki;
-    WH_HIP(hipMalloc(&b->d_st, (size_t)C * sizeof(MmState)));
+    WH_HIP(b->d_st.alloc((size_t)C));
     WH_HIP(hipMemset(b->d_st, 0, (size_t)C * sizeof(MmState)));
-    *out = guard.release();
+    *out = b.release();
     return WH_OK;
 }
 
-extern "C" void wh_mm_bank_destroy(wh_mm_bank *b) {
-    if (!b) return;
-    (void)hipFree(b->d_st);
-    delete b;
-}
+extern "C" void wh_mm_bank_destroy(wh_mm_bank *b) { delete b; }
 
 extern "C" int wh_mm_bank_reset(wh_mm_bank *b, void *stream) {
     if (!b) return set_err(WH_E_ARG, "wh_mm_bank_reset: null handle");

@@ -183,24 +183,19 @@ __global__ __launch_bounds__(256) void bch_decode_kernel(const uint64_t *cw, con
 }  // namespace
 
 struct wh_bch {
-    uint64_t *d_cw = nullptr;
+    DevBuf<uint64_t> d_cw;
 };
 
 extern "C" int wh_bch_create(wh_bch **out, const uint64_t *h_codewords) {
     if (!out || !h_codewords) return set_err(WH_E_ARG, "wh_bch_create: null");
-    wh_bch *b = new wh_bch();
-    std::unique_ptr<wh_bch, void (*)(wh_bch *)> guard(b, wh_bch_destroy);  // frees partial state on early return
-    WH_HIP(hipMalloc(&b->d_cw, 65536 * sizeof(uint64_t)));
+    std::unique_ptr<wh_bch> b(new wh_bch());   // frees partial state on early return
+    WH_HIP(b->d_cw.alloc(65536));
     WH_HIP(hipMemcpy(b->d_cw, h_codewords, 65536 * sizeof(uint64_t), hipMemcpyHostToDevice));
-    *out = guard.release();
+    *out = b.release();
     return WH_OK;
 }
 
-extern "C" void wh_bch_destroy(wh_bch *b) {
-    if (!b) return;
-    (void)hipFree(b->d_cw);
-    delete b;
-}
+extern "C" void wh_bch_destroy(wh_bch *b) { delete b; }
 
 extern "C" int wh_bch_decode(wh_bch *b, const uint64_t *d_words, size_t n, const int32_t *d_tracked_nac, int32_t *d_data,
                              int32_t *d_errors, void *stream) {

@@ -405,10 +405,10 @@ static constexpr int LSM_WAVE_FORM_MAX_CHANNELS = 2048;
 struct wh_lsm_bank {
     int C, n_max;
     double sps;
-    float *d_lpf = nullptr, *d_mmse = nullptr;
-    LsmState *d_st = nullptr;
-    LsmCall *d_call = nullptr;
-    float2 *d_hist = nullptr, *d_filt = nullptr;
+    DevBuf<float> d_lpf, d_mmse;
+    DevBuf<LsmState> d_st;
+    DevBuf<LsmCall> d_call;
+    DevBuf<float2> d_hist, d_filt;
 };
 
 static int lsm_reset(wh_lsm_bank *b, hipStream_t st) {
@@ -428,41 +428,35 @@ extern "C" int wh_lsm_bank_create(wh_lsm_bank **out, int C, double sps, const fl
                                   int n_max) {
     if (!out || !h_lpf || !h_mmse || C < 1 || !(sps >= 2.0) || !(sps < 1e6) || n_max < 1)
         return set_err(WH_E_ARG, "wh_lsm_bank_create: bad arguments");
-    wh_lsm_bank *b = new wh_lsm_bank();
-    std::unique_ptr<wh_lsm_bank, void (*)(wh_lsm_bank *)> guard(b, wh_lsm_bank_destroy);  // frees partial state on early return
+    std::unique_ptr<wh_lsm_bank> b(new wh_lsm_bank());   // frees partial state on early return
     b->C = C; b->n_max = n_max; b->sps = sps;
-    WH_HIP(hipMalloc(&b->d_lpf, NLPF * sizeof(float)));
-    WH_HIP(hipMalloc(&b->d_mmse, 129 * 8 * sizeof(float)));
+    WH_HIP(b->d_lpf.alloc(NLPF));
+    WH_HIP(b->d_mmse.alloc(129 * 8));
     WH_HIP(hipMemcpy(b->d_lpf, h_lpf, NLPF * sizeof(float), hipMemcpyHostToDevice));
     WH_HIP(hipMemcpy(b->d_mmse, h_mmse, 129 * 8 * sizeof(float), hipMemcpyHostToDevice));
-    WH_HIP(hipMalloc(&b->d_st, (size_t)C * sizeof(LsmState)));
-    WH_HIP(hipMalloc(&b->d_call, (size_t)C * sizeof(LsmCall)));
-    WH_HIP(hipMalloc(&b->d_hist, (size_t)C * NT * sizeof(float2)));
-    WH_HIP(hipMalloc(&b->d_filt, (size_t)C * (NT + (size_t)n_max) * sizeof(float2)));
-    int rc = lsm_reset(b, nullptr);
+    WH_HIP(b->d_st.alloc((size_t)C));
+    WH_HIP(b->d_call.alloc((size_t)C));
+    WH_HIP(b->d_hist.alloc((size_t)C * NT));
+    WH_HIP(b->d_filt.alloc((size_t)C * (NT + (size_t)n_max)));
+    int rc = lsm_reset(b.get(), nullptr);
     if (rc != WH_OK) return rc;
-    *out = guard.release();
+    *out = b.release();
     return WH_OK;
 }
 
-extern "C" void wh_lsm_bank_destroy(wh_lsm_bank *b) {
-    if (!b) return;
-    (void)hipFree(b->d_lpf); (void)hipFree(b->d_mmse); (void)hipFree(b->d_st); (void)hipFree(b->d_call);
-    (void)hipFree(b->d_hist); (void)hipFree(b->d_filt);
-    delete b;
-}
+extern "C" void wh_lsm_bank_destroy(wh_lsm_bank *b) { delete b; }
 
 // The reference's demodulate(iq) takes a call of any length (decoders/p25.py:413); only the per-call work buffer of the
 // low-passed samples depends on the call size -- the carried state (AGC, loops, filter history) does not -- so a longer call
-// than the bank was created for grows that buffer and nothing else.  Synchronises the stream (a steady caller never grows).
+// than the bank was created for grows that buffer and nothing else.  Synchronises the stream and the device (a steady
+// caller never grows).
 extern "C" int wh_lsm_bank_reserve(wh_lsm_bank *b, int n_max, void *stream) {
     if (!b || n_max < 1) return set_err(WH_E_ARG, "wh_lsm_bank_reserve: bad arguments");
     if (n_max <= b->n_max) return WH_OK;
-    WH_HIP(hipStreamSynchronize(as_stream(stream)));
-    float2 *nf = nullptr;
-    WH_HIP(hipMalloc(&nf, (size_t)b->C * (NT + (size_t)n_max) * sizeof(float2)));
-    (void)hipFree(b->d_filt);
-    b->d_filt = nf;
+    DevBuf<float2> filt;
+    WH_HIP(filt.alloc((size_t)b->C * (NT + (size_t)n_max)));
+    WH_HIP(sync_before_swap(as_stream(stream)));
+    b->d_filt = std::move(filt);
     b->n_max = n_max;
     return WH_OK;
 }

@@ -1026,14 +1026,14 @@ __global__ void stats_merge_kernel(const double *g, int R, int M, double *out) {
 
 struct wh_pfb {
     int M, T, log2M;
-    float *d_arms = nullptr;    // [M][T] float32
-    float2 *d_tw = nullptr;     // [M]
-    float2 *d_hist[2] = {nullptr, nullptr};
+    DevBuf<float> d_arms;       // [M][T] float32
+    DevBuf<float2> d_tw;        // [M]
+    DevBuf<float2> d_hist[2];
     int cur = 0;
-    double *d_part = nullptr;   // stats partials
-    float2 *d_sink = nullptr;   // [M] write-only scratch row of the shaped kernels
-    float2 *d_edge = nullptr;   // M = 1024 statistics-only mode: outputs of the <= 8 head and <= 3 tail hops [11][1024]
-    double *d_stats_ws = nullptr;   // statistics-only mode: one [4][M] row per workgroup of the launch
+    DevBuf<double> d_part;      // stats partials
+    DevBuf<float2> d_sink;      // [M] write-only scratch row of the shaped kernels
+    DevBuf<float2> d_edge;      // M = 1024 statistics-only mode: outputs of the <= 8 head and <= 3 tail hops [11][1024]
+    DevBuf<double> d_stats_ws;  // statistics-only mode: one [4][M] row per workgroup of the launch
     size_t stats_ws_rows = 0;
     int cu_count = 256;
     int gpw_override = 0;       // wh_pfb_tune(WH_PFB_TUNE_HOPS_PER_RUN)
@@ -1098,13 +1098,13 @@ extern "C" int wh_pfb_create(wh_pfb **out, int M, int T, const double *h_arms) {
             p->side = nullptr;
         }
     }
-    WH_HIP(hipMalloc(&p->d_arms, arms.size() * sizeof(float)));
-    WH_HIP(hipMalloc(&p->d_tw, tw.size() * sizeof(float2)));
-    WH_HIP(hipMalloc(&p->d_hist[0], (size_t)M * T * sizeof(float2)));
-    WH_HIP(hipMalloc(&p->d_hist[1], (size_t)M * T * sizeof(float2)));
-    WH_HIP(hipMalloc(&p->d_part, (size_t)64 * M * 4 * sizeof(double)));
-    WH_HIP(hipMalloc(&p->d_sink, (size_t)M * sizeof(float2)));
-    if (M == FM && T == FT) WH_HIP(hipMalloc(&p->d_edge, (size_t)11 * FM * sizeof(float2)));
+    WH_HIP(p->d_arms.alloc(arms.size()));
+    WH_HIP(p->d_tw.alloc(tw.size()));
+    WH_HIP(p->d_hist[0].alloc((size_t)M * T));
+    WH_HIP(p->d_hist[1].alloc((size_t)M * T));
+    WH_HIP(p->d_part.alloc((size_t)64 * M * 4));
+    WH_HIP(p->d_sink.alloc((size_t)M));
+    if (M == FM && T == FT) WH_HIP(p->d_edge.alloc((size_t)11 * FM));
     WH_HIP(hipMemcpy(p->d_arms, arms.data(), arms.size() * sizeof(float), hipMemcpyHostToDevice));
     WH_HIP(hipMemcpy(p->d_tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice));
     WH_HIP(hipMemset(p->d_hist[0], 0, (size_t)M * T * sizeof(float2)));
@@ -1113,16 +1113,9 @@ extern "C" int wh_pfb_create(wh_pfb **out, int M, int T, const double *h_arms) {
     return WH_OK;
 }
 
+// the device buffers are DevBufs; the side stream and the events are released here
 extern "C" void wh_pfb_destroy(wh_pfb *p) {
     if (!p) return;
-    (void)hipFree(p->d_arms);
-    (void)hipFree(p->d_tw);
-    (void)hipFree(p->d_hist[0]);
-    (void)hipFree(p->d_hist[1]);
-    (void)hipFree(p->d_part);
-    (void)hipFree(p->d_sink);
-    (void)hipFree(p->d_edge);
-    (void)hipFree(p->d_stats_ws);
     for (int i = 0; i < wh_pfb::EVR; ++i) {
         if (p->ev0[i]) (void)hipEventDestroy(p->ev0[i]);
         if (p->ev1[i]) (void)hipEventDestroy(p->ev1[i]);
@@ -1537,6 +1530,17 @@ extern "C" int wh_diag_stream_1r4w(const float *d_in, float *d_out, size_t n, vo
     return WH_OK;
 }
 
+// grow the statistics workspace to `rows` rows of [4][M] (synchronises; a steady call size never does)
+static int pfb_stats_ws_reserve(wh_pfb *p, size_t rows, hipStream_t st) {
+    if (rows <= p->stats_ws_rows) return WH_OK;
+    DevBuf<double> ws;
+    WH_HIP(ws.alloc(rows * 4 * p->M));
+    WH_HIP(sync_before_swap(st));
+    p->d_stats_ws = std::move(ws);
+    p->stats_ws_rows = rows;
+    return WH_OK;
+}
+
 extern "C" int wh_pfb_run_stats(wh_pfb *p, const void *d_iq, int input_format, size_t n, double *d_stats, int accumulate,
                                 void *stream) {
     if (!p) return set_err(WH_E_ARG, "wh_pfb_run_stats: null handle");
@@ -1574,14 +1578,7 @@ extern "C" int wh_pfb_run_stats(wh_pfb *p, const void *d_iq, int input_format, s
 #ifdef WH_DIAG
             a.ablate = 0;
 #endif
-            if ((size_t)nwg > p->stats_ws_rows) {   // rows of [4][M]: grow (synchronises; a steady call size never does)
-                WH_HIP(hipStreamSynchronize(st));
-                (void)hipFree(p->d_stats_ws);
-                p->d_stats_ws = nullptr;
-                p->stats_ws_rows = 0;
-                WH_HIP(hipMalloc(&p->d_stats_ws, (size_t)nwg * 4 * p->M * sizeof(double)));
-                p->stats_ws_rows = (size_t)nwg;
-            }
+            if ((rc = pfb_stats_ws_reserve(p, (size_t)nwg, st)) != WH_OK) return rc;
             a.stats_ws = p->d_stats_ws;
             if (p->prof) WH_HIP(hipEventRecord(p->ev0[p->ev_begin()], st));
             if (input_format == 1) hipLaunchKernelGGL((pfb1024_kernel<1, true, true>), dim3((unsigned)nwg), dim3(256), 0, st, a);
@@ -1595,9 +1592,9 @@ extern "C" int wh_pfb_run_stats(wh_pfb *p, const void *d_iq, int input_format, s
                 return rc;
             acc = 1;
         }
-        if ((rc = launch_generic(p, d_iq, input_format, reinterpret_cast<float *>(p->d_edge), 0, head, st, tail0, tailn, head)) != WH_OK)
+        if ((rc = launch_generic(p, d_iq, input_format, reinterpret_cast<float *>(p->d_edge.get()), 0, head, st, tail0, tailn, head)) != WH_OK)
             return rc;
-        if ((rc = wh_pfb_channel_stats(p, reinterpret_cast<const float *>(p->d_edge), (size_t)(head + tailn), d_stats, acc, stream)) != WH_OK)
+        if ((rc = wh_pfb_channel_stats(p, reinterpret_cast<const float *>(p->d_edge.get()), (size_t)(head + tailn), d_stats, acc, stream)) != WH_OK)
             return rc;
         int nxt = p->cur ^ 1;
         int tot = p->M * p->T;
@@ -1617,14 +1614,7 @@ extern "C" int wh_pfb_run_stats(wh_pfb *p, const void *d_iq, int input_format, s
     long long grid = 0;
     int rc = pfb_mid_launch(p->M, p->T, c, st, &grid);
     if (rc != WH_OK) return rc;
-    if ((size_t)grid > p->stats_ws_rows) {      // grow the workspace (synchronises; a steady call size never does)
-        WH_HIP(hipStreamSynchronize(st));
-        (void)hipFree(p->d_stats_ws);
-        p->d_stats_ws = nullptr;
-        p->stats_ws_rows = 0;
-        WH_HIP(hipMalloc(&p->d_stats_ws, (size_t)grid * 4 * p->M * sizeof(double)));
-        p->stats_ws_rows = (size_t)grid;
-    }
+    if ((rc = pfb_stats_ws_reserve(p, (size_t)grid, st)) != WH_OK) return rc;
     c.stats_ws = p->d_stats_ws;
     if (p->prof) WH_HIP(hipEventRecord(p->ev0[p->ev_begin()], st));
     if ((rc = pfb_mid_launch(p->M, p->T, c, st)) != WH_OK) return rc;

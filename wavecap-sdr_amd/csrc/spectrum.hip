@@ -118,9 +118,9 @@ __global__ __launch_bounds__(256) void spectrum_post_kernel(const float2 *X, flo
 
 struct wh_spectrum {
     int N, log2N;
-    float *d_window = nullptr;
-    float2 *d_tw = nullptr;
-    float *d_sink = nullptr;   // [N] row for the shaped kernel's stores of frames past the end of a call
+    DevBuf<float> d_window;
+    DevBuf<float2> d_tw;
+    DevBuf<float> d_sink;   // [N] row for the shaped kernel's stores of frames past the end of a call
     size_t smem = 0;
     bool shaped = false;       // a shaped instance exists for N
     int path = 0;              // wh_spectrum_tune: 0 auto, 1 Stockham / DFT kernel, 2 shaped kernel
@@ -129,8 +129,7 @@ struct wh_spectrum {
 
 extern "C" int wh_spectrum_create(wh_spectrum **out, int N) {
     if (!out || N < 2 || N > 16384) return set_err(WH_E_ARG, "wh_spectrum_create: fft_size must be in [2, 16384]");
-    wh_spectrum *s = new wh_spectrum();
-    std::unique_ptr<wh_spectrum, void (*)(wh_spectrum *)> guard(s, wh_spectrum_destroy);  // frees partial state on early return
+    std::unique_ptr<wh_spectrum> s(new wh_spectrum());   // frees partial state on early return
     s->N = N;
     int l2 = 0;
     while ((1 << l2) < N) ++l2;
@@ -143,11 +142,11 @@ extern "C" int wh_spectrum_create(wh_spectrum **out, int N) {
         double ang = -2.0 * M_PI * (double)m / (double)N;
         tw[m] = make_float2((float)cos(ang), (float)sin(ang));
     }
-    WH_HIP(hipMalloc(&s->d_window, (size_t)N * sizeof(float)));
-    WH_HIP(hipMalloc(&s->d_tw, (size_t)N * sizeof(float2)));
+    WH_HIP(s->d_window.alloc((size_t)N));
+    WH_HIP(s->d_tw.alloc((size_t)N));
     WH_HIP(hipMemcpy(s->d_window, w.data(), (size_t)N * sizeof(float), hipMemcpyHostToDevice));
     WH_HIP(hipMemcpy(s->d_tw, tw.data(), (size_t)N * sizeof(float2), hipMemcpyHostToDevice));
-    WH_HIP(hipMalloc(&s->d_sink, (size_t)N * sizeof(float)));
+    WH_HIP(s->d_sink.alloc((size_t)N));
     s->shaped = spectrum_mid_supported(N);
     {
         int dev = 0;
@@ -160,17 +159,11 @@ extern "C" int wh_spectrum_create(wh_spectrum **out, int N) {
     if (s->smem > 64 * 1024)
         WH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(spectrum_kernel),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)s->smem));
-    *out = guard.release();
+    *out = s.release();
     return WH_OK;
 }
 
-extern "C" void wh_spectrum_destroy(wh_spectrum *s) {
-    if (!s) return;
-    (void)hipFree(s->d_window);
-    (void)hipFree(s->d_tw);
-    (void)hipFree(s->d_sink);
-    delete s;
-}
+extern "C" void wh_spectrum_destroy(wh_spectrum *s) { delete s; }
 
 extern "C" int wh_spectrum_run(wh_spectrum *s, const float *d_iq, size_t n_frames, size_t frame_stride,
                                float *d_power_db, void *stream) {

@@ -264,16 +264,12 @@ int pick_opw(int L, int D) {
 // ---- wh_ddc_bank, and wh_ddc as a bank of one ---------------------------------------------------
 struct wh_ddc_bank {
     int K, fs, L1, D1, L2, D2, max_n;
-    double *d_t1 = nullptr, *d_t2 = nullptr;
-    float2 *d_h1[2] = {nullptr, nullptr}, *d_h2[2] = {nullptr, nullptr};
-    float2 *d_mid = nullptr;
+    DevBuf<double> d_t1, d_t2;
+    DevBuf<float2> d_h1[2], d_h2[2];
+    DevBuf<float2> d_mid;
     size_t mid_stride = 0;
     struct Chan { bool first = true; long long sample_idx = 0; double last_offset = 0.0; int cur = 0; };
     std::vector<Chan> ch;
-    ~wh_ddc_bank() {
-        (void)hipFree(d_t1); (void)hipFree(d_t2); (void)hipFree(d_mid);
-        for (int i = 0; i < 2; ++i) { (void)hipFree(d_h1[i]); (void)hipFree(d_h2[i]); }
-    }
 };
 
 struct wh_ddc : wh_ddc_bank {};
@@ -284,15 +280,15 @@ static int ddc_bank_init(wh_ddc_bank *d, int n_channels, int sample_rate, const 
     d->K = n_channels; d->fs = sample_rate; d->L1 = n1; d->D1 = d1; d->L2 = d2 > 1 ? n2 : 0; d->D2 = d2 > 1 ? d2 : 1;
     d->max_n = max_samples_per_call;
     d->ch.resize(n_channels);
-    WH_HIP(hipMalloc(&d->d_t1, n1 * sizeof(double)));
+    WH_HIP(d->d_t1.alloc(n1));
     WH_HIP(hipMemcpy(d->d_t1, h_taps1, n1 * sizeof(double), hipMemcpyHostToDevice));
-    for (int i = 0; i < 2; ++i) WH_HIP(hipMalloc(&d->d_h1[i], (size_t)n_channels * (n1 > 1 ? n1 - 1 : 1) * sizeof(float2)));
+    for (int i = 0; i < 2; ++i) WH_HIP(d->d_h1[i].alloc((size_t)n_channels * (n1 > 1 ? n1 - 1 : 1)));
     if (d->L2) {
-        WH_HIP(hipMalloc(&d->d_t2, n2 * sizeof(double)));
+        WH_HIP(d->d_t2.alloc(n2));
         WH_HIP(hipMemcpy(d->d_t2, h_taps2, n2 * sizeof(double), hipMemcpyHostToDevice));
-        for (int i = 0; i < 2; ++i) WH_HIP(hipMalloc(&d->d_h2[i], (size_t)n_channels * (n2 > 1 ? n2 - 1 : 1) * sizeof(float2)));
+        for (int i = 0; i < 2; ++i) WH_HIP(d->d_h2[i].alloc((size_t)n_channels * (n2 > 1 ? n2 - 1 : 1)));
         d->mid_stride = (size_t)max_samples_per_call / d1 + 2;
-        WH_HIP(hipMalloc(&d->d_mid, (size_t)n_channels * d->mid_stride * sizeof(float2)));
+        WH_HIP(d->d_mid.alloc((size_t)n_channels * d->mid_stride));
     }
     return WH_OK;
 }

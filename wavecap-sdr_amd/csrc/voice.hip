@@ -412,26 +412,24 @@ DiscState fresh_state() {
 struct wh_disc_bank {
     int C, n_max, nbb;
     double symtime;
-    float *d_bb = nullptr, *d_mmse = nullptr;
-    DiscState *d_st = nullptr;
-    int *d_go = nullptr;
-    double2 *d_pc = nullptr;
-    float *d_w = nullptr, *d_f = nullptr;
+    DevBuf<float> d_bb, d_mmse;
+    DevBuf<DiscState> d_st;
+    DevBuf<int> d_go;
+    DevBuf<double2> d_pc;
+    DevBuf<float> d_w, d_f;
 };
 
-static int disc_alloc_work(wh_disc_bank *b, int n_max) {
-    double2 *pc = nullptr;
-    float *w = nullptr, *f = nullptr;
+static int disc_alloc_work(wh_disc_bank *b, int n_max, hipStream_t st) {
+    DevBuf<double2> pc;
+    DevBuf<float> w, f;
     const size_t m = (size_t)b->C * (size_t)n_max;
-    hipError_t e = hipMalloc(&pc, m * sizeof(double2));
-    if (e == hipSuccess) e = hipMalloc(&w, m * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&f, m * sizeof(float));
-    if (e != hipSuccess) {
-        (void)hipFree(pc); (void)hipFree(w); (void)hipFree(f);
+    hipError_t e = pc.alloc(m);
+    if (e == hipSuccess) e = w.alloc(m);
+    if (e == hipSuccess) e = f.alloc(m);
+    if (e == hipSuccess) e = sync_before_swap(st);
+    if (e != hipSuccess)
         return set_err(WH_E_HIP, "wh_disc_bank: work buffers of %d x %d samples -> %s", b->C, n_max, hipGetErrorString(e));
-    }
-    (void)hipFree(b->d_pc); (void)hipFree(b->d_w); (void)hipFree(b->d_f);
-    b->d_pc = pc; b->d_w = w; b->d_f = f;
+    b->d_pc = std::move(pc); b->d_w = std::move(w); b->d_f = std::move(f);
     b->n_max = n_max;
     return WH_OK;
 }
@@ -443,39 +441,33 @@ extern "C" int wh_disc_bank_create(wh_disc_bank **out, int n_channels, double sa
         n_bb % 2 == 0 || max_samples_per_call < 1 || max_samples_per_call > (size_t)1 << 26)
         return set_err(WH_E_ARG, "wh_disc_bank_create: bad arguments (1..%d channels, odd n_bb <= %d, "
                                  "1 <= max_samples_per_call <= 2^26)", WH_DISC_MAX_CHANNELS, MAX_BB);
-    wh_disc_bank *b = new wh_disc_bank();
-    std::unique_ptr<wh_disc_bank, void (*)(wh_disc_bank *)> guard(b, wh_disc_bank_destroy);
+    std::unique_ptr<wh_disc_bank> b(new wh_disc_bank());
     b->C = n_channels; b->nbb = n_bb; b->n_max = 0;
     b->symtime = symbol_rate / sample_rate;
-    WH_HIP(hipMalloc(&b->d_bb, n_bb * sizeof(float)));
-    WH_HIP(hipMalloc(&b->d_mmse, (NSTEPS + 1) * NT * sizeof(float)));
+    WH_HIP(b->d_bb.alloc(n_bb));
+    WH_HIP(b->d_mmse.alloc((NSTEPS + 1) * NT));
     WH_HIP(hipMemcpy(b->d_bb, h_bb_taps, n_bb * sizeof(float), hipMemcpyHostToDevice));
     WH_HIP(hipMemcpy(b->d_mmse, h_mmse, (NSTEPS + 1) * NT * sizeof(float), hipMemcpyHostToDevice));
-    WH_HIP(hipMalloc(&b->d_st, (size_t)n_channels * sizeof(DiscState)));
-    WH_HIP(hipMalloc(&b->d_go, (size_t)n_channels * sizeof(int)));
-    int rc = disc_alloc_work(b, (int)max_samples_per_call);
+    WH_HIP(b->d_st.alloc((size_t)n_channels));
+    WH_HIP(b->d_go.alloc((size_t)n_channels));
+    int rc = disc_alloc_work(b.get(), (int)max_samples_per_call, nullptr);
     if (rc != WH_OK) return rc;
     std::vector<DiscState> z((size_t)n_channels, fresh_state());
     WH_HIP(hipMemcpy(b->d_st, z.data(), z.size() * sizeof(DiscState), hipMemcpyHostToDevice));
-    *out = guard.release();
+    *out = b.release();
     return WH_OK;
 }
 
-extern "C" void wh_disc_bank_destroy(wh_disc_bank *b) {
-    if (!b) return;
-    (void)hipFree(b->d_bb); (void)hipFree(b->d_mmse); (void)hipFree(b->d_st); (void)hipFree(b->d_go);
-    (void)hipFree(b->d_pc); (void)hipFree(b->d_w); (void)hipFree(b->d_f);
-    delete b;
-}
+extern "C" void wh_disc_bank_destroy(wh_disc_bank *b) { delete b; }
 
 // Only the per-call work buffers depend on the call length; the carried state does not, so a longer call than the bank
-// was created for grows them and keeps every channel's state.  Synchronises the stream (a steady caller never grows).
+// was created for grows them and keeps every channel's state.  Synchronises the stream and the device (a steady caller
+// never grows).
 extern "C" int wh_disc_bank_reserve(wh_disc_bank *b, size_t max_samples_per_call, void *stream) {
     if (!b || max_samples_per_call < 1 || max_samples_per_call > (size_t)1 << 26)
         return set_err(WH_E_ARG, "wh_disc_bank_reserve: bad arguments");
     if (max_samples_per_call <= (size_t)b->n_max) return WH_OK;
-    WH_HIP(hipStreamSynchronize(as_stream(stream)));
-    return disc_alloc_work(b, (int)max_samples_per_call);
+    return disc_alloc_work(b, (int)max_samples_per_call, as_stream(stream));
 }
 
 // full = 0: DiscriminatorDemodulator.reset() (p25.py:1335-1345; keeps the input gain, and the recorder keeps its phase);

@@ -4,6 +4,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <utility>
 #include "../../include/wavehip.h"
 
 namespace wh {
@@ -95,5 +96,55 @@ __device__ __forceinline__ void fft16(float2 (&v)[16]) {
 }
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
+
+// Owning device buffer of n elements of T: move-only, hipFree on destruction.  Converts to T * so that kernel
+// argument structs and launches take it as a raw pointer.
+template <class T>
+class DevBuf {
+  public:
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    DevBuf(DevBuf &&o) noexcept : p_(std::exchange(o.p_, nullptr)), n_(std::exchange(o.n_, 0)) {}
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) {
+            release();
+            p_ = std::exchange(o.p_, nullptr);
+            n_ = std::exchange(o.n_, 0);
+        }
+        return *this;
+    }
+    ~DevBuf() { release(); }
+
+    // replaces the contents with n uninitialised elements; on failure the buffer is left empty
+    hipError_t alloc(size_t n) {
+        release();
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&p_), n * sizeof(T));
+        if (e != hipSuccess) p_ = nullptr;
+        else n_ = n;
+        return e;
+    }
+    T *get() const { return p_; }
+    operator T *() const { return p_; }
+    size_t size() const { return n_; }
+
+  private:
+    void release() {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+        n_ = 0;
+    }
+    T *p_ = nullptr;
+    size_t n_ = 0;
+};
+
+// The one rule for growing a handle's workspaces at run time: allocate the new buffers into local DevBufs first (a
+// failure returns with the handle untouched), enqueue any carried copy on the caller's stream, then call this before
+// moving them into the handle.  It waits for the caller's stream (the copies) and then the device: earlier calls, on
+// whichever stream, may still use the old buffers, which are freed when the moves replace them.
+inline hipError_t sync_before_swap(hipStream_t st) {
+    hipError_t e = hipStreamSynchronize(st);
+    return e == hipSuccess ? hipDeviceSynchronize() : e;
+}
 
 }  // namespace wh

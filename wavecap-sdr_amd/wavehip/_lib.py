@@ -217,6 +217,61 @@ class Handle:
             self._h = None
 
 
+class SymbolBank(Handle):
+    """Base of the symbol banks (C4FM, CQPSK, LSM, discriminator): C channels, one reference call per channel and call,
+    device workspaces sized for calls of up to `max_samples_per_call` samples.  A subclass sets `_prefix` (wh_x_bank)
+    and `_growth`, and sizes its own output buffers in `_size_outputs()`."""
+
+    _prefix = ""
+    _growth = 1.0   # a call longer than any before grows the bank to max(n, growth x the current size)
+
+    def _create_bank(self, *args) -> None:
+        self._create(self._prefix, *args)
+        self._counts = self._torch.zeros(self.n_channels, dtype=self._torch.int32, device="cuda")
+        self._size_outputs()
+
+    def _size_outputs(self) -> None:
+        raise NotImplementedError
+
+    def reserve(self, max_samples_per_call: int) -> None:
+        """Grow the bank for calls of up to `max_samples_per_call` samples per channel (allocates and synchronises; all
+        demodulator state is kept).  A longer call does it by itself; call it up front to keep the allocation out of
+        that call."""
+        if max_samples_per_call <= self.max_samples_per_call:
+            return
+        fn = self._prefix + "_reserve"
+        check(getattr(lib, fn)(self._h, int(max_samples_per_call), stream_ptr(self._torch)), fn)
+        self.max_samples_per_call = int(max_samples_per_call)
+        self._size_outputs()
+
+    def _grow_for(self, n: int) -> None:
+        if n > self.max_samples_per_call:
+            # a call is never split (the reference is not invariant to where a stream is cut): grow, keep the state
+            self.reserve(max(n, int(self.max_samples_per_call * self._growth)))
+
+    def reset(self) -> None:
+        fn = self._prefix + "_reset"
+        check(getattr(lib, fn)(self._h, stream_ptr(self._torch)), fn)
+
+    def _call_shape(self, x, dtype) -> tuple[int, int]:
+        """Checks a [C, n] GPU tensor of `dtype` with unit-stride rows -> (n, row stride)."""
+        assert x.is_cuda and x.dtype == dtype and x.dim() == 2
+        assert x.shape[0] == self.n_channels and x.stride(1) == 1
+        n = x.shape[1]
+        return n, (x.stride(0) if self.n_channels > 1 else n)   # a size-1 dim may report any stride
+
+    def _to_host(self, counts, *bufs) -> list:
+        """Device counts [C] and [C, cap] buffers -> per buffer, the list of each channel's counts[c] leading entries
+        (one copy of the [:, :max(counts)] prefix per buffer)."""
+        cnt = counts.cpu().numpy()
+        m = int(cnt.max())
+        out = []
+        for b in bufs:
+            h = b[:, :m].cpu().numpy()
+            out.append([h[c, :cnt[c]].copy() for c in range(self.n_channels)])
+        return out
+
+
 def dptr(arr, dtype: str) -> C.POINTER:
     """Host numpy array -> typed ctypes pointer (keeps no reference: caller holds the array)."""
     import numpy as np

@@ -58,8 +58,10 @@ def design_rrc_filter(samples_per_symbol: float, num_taps: int = 101, alpha: flo
     return (h / np.sum(h)).astype(np.float32)
 
 
-class C4FMBank(_lib.Handle):
+class C4FMBank(_lib.SymbolBank):
     """C independent C4FM demodulators, one wavefront each for the feedback part."""
+
+    _prefix = "wh_c4fm_bank"
 
     def __init__(self, n_channels: int, sample_rate: int = 19200, symbol_rate: int = SYMBOL_RATE,
                  wide_pulse: bool = False, max_samples_per_call: int = 16384):
@@ -75,12 +77,9 @@ class C4FMBank(_lib.Handle):
                                              num_taps=int(16 * self.samples_per_symbol) + 1, alpha=alpha)
         taps = np.ascontiguousarray(np.load(_TAPS_FILE), dtype=np.float32)
         assert taps.shape == (129, 8)
-        self._create("wh_c4fm_bank", self.n_channels, float(self.samples_per_symbol),
-                     _lib.dptr(self._baseband_lpf, "f32"), len(self._baseband_lpf),
-                     _lib.dptr(self._rrc_filter, "f32"), len(self._rrc_filter), _lib.dptr(taps, "f32"),
-                     self.max_samples_per_call)
-        self._counts = self._torch.zeros(self.n_channels, dtype=self._torch.int32, device="cuda")
-        self._size_outputs()
+        self._create_bank(self.n_channels, float(self.samples_per_symbol), _lib.dptr(self._baseband_lpf, "f32"),
+                          len(self._baseband_lpf), _lib.dptr(self._rrc_filter, "f32"), len(self._rrc_filter),
+                          _lib.dptr(taps, "f32"), self.max_samples_per_call)
 
     def _size_outputs(self) -> None:
         torch = self._torch
@@ -88,31 +87,14 @@ class C4FMBank(_lib.Handle):
         self._dibits = torch.empty((self.n_channels, self.out_cap), dtype=torch.uint8, device="cuda")
         self._soft = torch.empty((self.n_channels, self.out_cap), dtype=torch.float32, device="cuda")
 
-    def reserve(self, max_samples_per_call: int) -> None:
-        """Grow the bank for calls of up to `max_samples_per_call` samples per channel (allocates; all demodulator state
-        is kept).  Done implicitly by a longer call; call it up front to keep allocation out of the first long call."""
-        if max_samples_per_call <= self.max_samples_per_call:
-            return
-        _lib.check(_lib.lib.wh_c4fm_bank_reserve(self._h, int(max_samples_per_call), _lib.stream_ptr(self._torch)),
-                   "wh_c4fm_bank_reserve")
-        self.max_samples_per_call = int(max_samples_per_call)
-        self._size_outputs()
-
-    def reset(self) -> None:
-        _lib.check(_lib.lib.wh_c4fm_bank_reset(self._h, _lib.stream_ptr(self._torch)), "wh_c4fm_bank_reset")
-
     def demodulate_device(self, iq_dev):
         """iq_dev: complex64 GPU tensor [C, n] = ONE reference call per channel (a longer n than any before grows the
         workspaces first).  Returns GPU tensors
         (dibits uint8 [C, cap], soft float32 [C, cap], counts int32 [C]); rows are valid up to counts[c]
         and are overwritten by the next call."""
         torch = self._torch
-        assert iq_dev.is_cuda and iq_dev.dtype == torch.complex64 and iq_dev.dim() == 2
-        assert iq_dev.shape[0] == self.n_channels and iq_dev.stride(1) == 1
-        n = iq_dev.shape[1]
-        if n > self.max_samples_per_call:
-            self.reserve(n)
-        row_stride = iq_dev.stride(0) if self.n_channels > 1 else n   # a size-1 dim may report any stride
+        n, row_stride = self._call_shape(iq_dev, torch.complex64)
+        self._grow_for(n)
         _lib.check(_lib.lib.wh_c4fm_bank_run(self._h, iq_dev.data_ptr(), n, row_stride,
                                              self._dibits.data_ptr(), self._soft.data_ptr(), self.out_cap,
                                              self._counts.data_ptr(), _lib.stream_ptr(torch)), "wh_c4fm_bank_run")
@@ -126,8 +108,7 @@ class C4FMBank(_lib.Handle):
         if x.shape[1] == 0:
             return [(np.array([], dtype=np.uint8), np.array([], dtype=np.float32))] * self.n_channels
         d, sf, cnt = self.demodulate_device(torch.from_numpy(x).cuda())
-        d, sf, cnt = d.cpu().numpy(), sf.cpu().numpy(), cnt.cpu().numpy()
-        return [(d[c, :cnt[c]].copy(), sf[c, :cnt[c]].copy()) for c in range(self.n_channels)]
+        return list(zip(*self._to_host(cnt, d, sf)))
 
 
 class C4FMDemodulator:

@@ -41,7 +41,9 @@ def design_rrc_filter_phase2(samples_per_symbol: float, num_taps: int = 65, alph
     return np.asarray(h / np.sqrt(np.sum(h ** 2)), dtype=np.float32)
 
 
-class CQPSKBank(_lib.Handle):
+class CQPSKBank(_lib.SymbolBank):
+    _prefix = "wh_cqpsk_bank"
+
     def __init__(self, n_channels: int, sample_rate: int = 48000, symbol_rate: int = 12000, rrc_alpha: float = 1.0,
                  rrc_taps: int = 65, carrier_loop_bw: float = 0.01, timing_loop_bw: float = 0.01,
                  max_samples_per_call: int = 1 << 16):
@@ -54,11 +56,8 @@ class CQPSKBank(_lib.Handle):
         zi = np.ascontiguousarray(signal.lfilter_zi(self._rrc, 1.0), dtype=np.float64)
         ckp, cki = calculate_loop_coefficients(0.0, carrier_loop_bw, 0.707)      # cqpsk.py:107-110
         tkp, tki = calculate_loop_coefficients(self.samples_per_symbol, timing_loop_bw, 1.0)
-        self._create("wh_cqpsk_bank", self.n_channels, float(self.samples_per_symbol), _lib.dptr(self._rrc, "f32"),
-                     len(self._rrc), _lib.dptr(zi, "f64"), ckp, cki, 0.1, tkp, tki, self.max_samples_per_call)
-        self._counts = self._torch.zeros(self.n_channels, dtype=self._torch.int32, device="cuda")
-        self._symbols = None
-        self._size_outputs()
+        self._create_bank(self.n_channels, float(self.samples_per_symbol), _lib.dptr(self._rrc, "f32"), len(self._rrc),
+                          _lib.dptr(zi, "f64"), ckp, cki, 0.1, tkp, tki, self.max_samples_per_call)
 
     def _size_outputs(self) -> None:
         torch = self._torch
@@ -66,28 +65,12 @@ class CQPSKBank(_lib.Handle):
         self._dibits = torch.empty((self.n_channels, self.cap), dtype=torch.uint8, device="cuda")
         self._symbols = None        # complex128 [C, cap], allocated when symbols are first asked for
 
-    def reserve(self, max_samples_per_call: int) -> None:
-        """Grow the bank for calls of up to `max_samples_per_call` samples per channel (allocates; state is kept)."""
-        if max_samples_per_call <= self.max_samples_per_call:
-            return
-        _lib.check(_lib.lib.wh_cqpsk_bank_reserve(self._h, int(max_samples_per_call), _lib.stream_ptr(self._torch)),
-                   "wh_cqpsk_bank_reserve")
-        self.max_samples_per_call = int(max_samples_per_call)
-        self._size_outputs()
-
-    def reset(self) -> None:
-        _lib.check(_lib.lib.wh_cqpsk_bank_reset(self._h, _lib.stream_ptr(self._torch)), "wh_cqpsk_bank_reset")
-
     def demodulate_device(self, iq_dev, want_symbols: bool = False):
         torch = self._torch
-        assert iq_dev.is_cuda and iq_dev.dtype == torch.complex64 and iq_dev.dim() == 2
-        assert iq_dev.shape[0] == self.n_channels and iq_dev.stride(1) == 1
-        n = iq_dev.shape[1]
-        if n > self.max_samples_per_call:       # one call of the reference == one launch, whatever its length
-            self.reserve(n)
+        n, stride = self._call_shape(iq_dev, torch.complex64)
+        self._grow_for(n)       # one call of the reference == one launch, whatever its length
         if want_symbols and self._symbols is None:
             self._symbols = torch.empty((self.n_channels, self.cap), dtype=torch.complex128, device="cuda")
-        stride = iq_dev.stride(0) if self.n_channels > 1 else n
         _lib.check(_lib.lib.wh_cqpsk_bank_run(self._h, iq_dev.data_ptr(), n, stride, self._dibits.data_ptr(),
                                               self._symbols.data_ptr() if want_symbols else None, self.cap,
                                               self._counts.data_ptr(), _lib.stream_ptr(torch)), "wh_cqpsk_bank_run")
@@ -104,11 +87,9 @@ class CQPSKBank(_lib.Handle):
             e = np.array([], np.uint8)
             return [(e, np.zeros(0, np.complex128)) if want_symbols else e for _ in range(self.n_channels)]
         d, sy, cnt = self.demodulate_device(torch.from_numpy(x).cuda(), want_symbols)
-        d, cnt = d.cpu().numpy(), cnt.cpu().numpy()
-        sy = sy.cpu().numpy() if want_symbols else None
         if want_symbols:
-            return [(d[c, :cnt[c]].copy(), sy[c, :cnt[c]].copy()) for c in range(self.n_channels)]
-        return [d[c, :cnt[c]].copy() for c in range(self.n_channels)]
+            return list(zip(*self._to_host(cnt, d, sy)))
+        return self._to_host(cnt, d)[0]
 
 
 class CQPSKDemodulator:

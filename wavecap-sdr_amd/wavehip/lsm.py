@@ -44,7 +44,10 @@ def generate_mmse_taps() -> np.ndarray:
     return taps
 
 
-class LSMBank(_lib.Handle):
+class LSMBank(_lib.SymbolBank):
+    _prefix = "wh_lsm_bank"
+    _growth = 1.5
+
     def __init__(self, n_channels: int, sample_rate: int = 19200, symbol_rate: int = 4800,
                  max_samples_per_call: int = 1 << 17):
         self._torch = _lib.require_gpu()
@@ -54,27 +57,13 @@ class LSMBank(_lib.Handle):
         self.max_samples_per_call = int(max_samples_per_call)
         self._baseband_taps = np.ascontiguousarray(design_baseband_filter(sample_rate))
         self._mmse_taps = np.ascontiguousarray(generate_mmse_taps())
-        self._create("wh_lsm_bank", self.n_channels, float(self.samples_per_symbol), _lib.dptr(self._baseband_taps, "f32"),
-                     _lib.dptr(self._mmse_taps, "f32"), self.max_samples_per_call)
-        torch = self._torch
+        self._create_bank(self.n_channels, float(self.samples_per_symbol), _lib.dptr(self._baseband_taps, "f32"),
+                          _lib.dptr(self._mmse_taps, "f32"), self.max_samples_per_call)
+
+    def _size_outputs(self) -> None:
         self.cap = self.max_samples_per_call            # at most one symbol per sample
-        self._dibits = torch.empty((self.n_channels, self.cap), dtype=torch.uint8, device="cuda")
-        self._phases = None
-        self._counts = torch.zeros(self.n_channels, dtype=torch.int32, device="cuda")
-
-    def reset(self) -> None:
-        _lib.check(_lib.lib.wh_lsm_bank_reset(self._h, _lib.stream_ptr(self._torch)), "wh_lsm_bank_reset")
-
-    def reserve(self, max_samples_per_call: int) -> None:
-        """Grow the bank for calls of up to `max_samples_per_call` samples per channel (allocates; all demodulator state
-        is kept).  demodulate_device() does it by itself when a longer call arrives."""
-        if max_samples_per_call <= self.max_samples_per_call:
-            return
-        torch = self._torch
-        _lib.check(_lib.lib.wh_lsm_bank_reserve(self._h, int(max_samples_per_call), _lib.stream_ptr(torch)), "wh_lsm_bank_reserve")
-        self.max_samples_per_call = self.cap = int(max_samples_per_call)
-        self._dibits = torch.empty((self.n_channels, self.cap), dtype=torch.uint8, device="cuda")
-        self._phases = None
+        self._dibits = self._torch.empty((self.n_channels, self.cap), dtype=self._torch.uint8, device="cuda")
+        self._phases = None         # float32 [C, cap], allocated when phases are first asked for
 
     def state(self, channel: int = 0) -> dict:
         out = (C.c_double * 7)()
@@ -87,14 +76,10 @@ class LSMBank(_lib.Handle):
         """iq_dev complex64 GPU tensor [C, n] -> (dibits uint8 [C, cap], phases float32 [C, cap] | None,
         counts int32 [C]); the outputs are the bank's own buffers (valid until the next call)."""
         torch = self._torch
-        assert iq_dev.is_cuda and iq_dev.dtype == torch.complex64 and iq_dev.dim() == 2
-        assert iq_dev.shape[0] == self.n_channels and iq_dev.stride(1) == 1
-        n = iq_dev.shape[1]
-        if n > self.max_samples_per_call:
-            # the reference takes a call of any length (decoders/p25.py:413) and is NOT invariant to where a stream is cut
-            # (np.convolve(..., 'same') per call), so a long call is never split: the work buffers grow, state is kept
-            self.reserve(max(n, self.max_samples_per_call + self.max_samples_per_call // 2))
-        stride = iq_dev.stride(0) if self.n_channels > 1 else n
+        n, stride = self._call_shape(iq_dev, torch.complex64)
+        # the reference takes a call of any length (decoders/p25.py:413) and is NOT invariant to where a stream is cut
+        # (np.convolve(..., 'same') per call), so a long call is never split: the work buffers grow, state is kept
+        self._grow_for(n)
         if want_phases and self._phases is None:
             self._phases = torch.empty((self.n_channels, self.cap), dtype=torch.float32, device="cuda")
         _lib.check(_lib.lib.wh_lsm_bank_run(self._h, iq_dev.data_ptr(), n, stride, self._dibits.data_ptr(),
@@ -112,14 +97,9 @@ class LSMBank(_lib.Handle):
             e = [np.array([], dtype=np.uint8) for _ in range(self.n_channels)]
             return (e, [np.array([], dtype=np.float32) for _ in e]) if want_phases else e
         d, ph, cnt = self.demodulate_device(torch.from_numpy(x).cuda(), want_phases)
-        cnt = cnt.cpu().numpy()
-        m = int(cnt.max())
-        d = d[:, :m].cpu().numpy()
-        dib = [d[c, :cnt[c]].copy() for c in range(self.n_channels)]
         if not want_phases:
-            return dib
-        ph = ph[:, :m].cpu().numpy()
-        return dib, [ph[c, :cnt[c]].copy() for c in range(self.n_channels)]
+            return self._to_host(cnt, d)[0]
+        return tuple(self._to_host(cnt, d, ph))
 
 
 class CQPSKDemodulator:

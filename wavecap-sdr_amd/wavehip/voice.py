@@ -68,8 +68,11 @@ def _state_dict(out) -> dict:
     return d
 
 
-class DiscriminatorBank(_lib.Handle):
+class DiscriminatorBank(_lib.SymbolBank):
     """n_channels independent DiscriminatorDemodulators (one reference demodulate() call per channel and call)."""
+
+    _prefix = "wh_disc_bank"
+    _growth = 1.5
 
     def __init__(self, n_channels: int, sample_rate: int = 48000, symbol_rate: int = 4800,
                  max_samples_per_call: int = 1 << 14):
@@ -80,31 +83,12 @@ class DiscriminatorBank(_lib.Handle):
         self.max_samples_per_call = int(max_samples_per_call)
         self._baseband_taps = np.ascontiguousarray(design_baseband_filter(sample_rate))
         self._mmse_taps = np.ascontiguousarray(generate_mmse_taps())
-        self._create("wh_disc_bank", self.n_channels, float(sample_rate), float(symbol_rate),
-                     _lib.dptr(self._baseband_taps, "f32"), len(self._baseband_taps), _lib.dptr(self._mmse_taps, "f32"),
-                     self.max_samples_per_call)
-        self._alloc()
+        self._create_bank(self.n_channels, float(sample_rate), float(symbol_rate), _lib.dptr(self._baseband_taps, "f32"),
+                          len(self._baseband_taps), _lib.dptr(self._mmse_taps, "f32"), self.max_samples_per_call)
 
-    def _alloc(self) -> None:
-        torch = self._torch
+    def _size_outputs(self) -> None:
         self.cap = self.max_samples_per_call                 # at most one symbol per sample
-        self._dibits = torch.empty((self.n_channels, self.cap), dtype=torch.uint8, device="cuda")
-        self._counts = torch.zeros(self.n_channels, dtype=torch.int32, device="cuda")
-
-    def reserve(self, max_samples_per_call: int) -> None:
-        """Grow the bank for calls of up to `max_samples_per_call` samples per channel (allocates and synchronises; all
-        state is kept).  The demodulate calls do it by themselves when a longer call arrives."""
-        if max_samples_per_call <= self.max_samples_per_call:
-            return
-        _lib.check(_lib.lib.wh_disc_bank_reserve(self._h, int(max_samples_per_call), _lib.stream_ptr(self._torch)),
-                   "wh_disc_bank_reserve")
-        self.max_samples_per_call = int(max_samples_per_call)
-        self._alloc()
-
-    def _grow_for(self, n: int) -> None:
-        if n > self.max_samples_per_call:
-            # a call is never split (the reference is not invariant to where a stream is cut): grow, keep the state
-            self.reserve(max(n, self.max_samples_per_call + self.max_samples_per_call // 2))
+        self._dibits = self._torch.empty((self.n_channels, self.cap), dtype=self._torch.uint8, device="cuda")
 
     def reset(self, channel: int = -1, full: bool = False) -> None:
         """full=False: DiscriminatorDemodulator.reset() (keeps the input gain); full=True: a fresh demodulator."""
@@ -132,11 +116,8 @@ class DiscriminatorBank(_lib.Handle):
         bank's own buffers (valid until the next call).  Inactive channels and rows holding a non-finite sample keep
         their state and report 0 symbols."""
         torch = self._torch
-        assert audio_dev.is_cuda and audio_dev.dtype == torch.float32 and audio_dev.dim() == 2
-        assert audio_dev.shape[0] == self.n_channels and audio_dev.stride(1) == 1
-        n = audio_dev.shape[1]
+        n, stride = self._call_shape(audio_dev, torch.float32)
         self._grow_for(n)
-        stride = audio_dev.stride(0) if self.n_channels > 1 else n
         act = self._mask(active, self.n_channels)
         _lib.check(_lib.lib.wh_disc_bank_run(self._h, audio_dev.data_ptr(), n, stride,
                                              None if act is None else act.ctypes.data, self._dibits.data_ptr(),
@@ -148,11 +129,8 @@ class DiscriminatorBank(_lib.Handle):
         """iq_dev complex64 GPU tensor [C, n] of decimated IQ -> discriminator (float64 angle, unwrap against the
         carried phase, diff) -> demodulator.  disc_out (optional) float32 [C, >= n] receives the disc audio."""
         torch = self._torch
-        assert iq_dev.is_cuda and iq_dev.dtype == torch.complex64 and iq_dev.dim() == 2
-        assert iq_dev.shape[0] == self.n_channels and iq_dev.stride(1) == 1
-        n = iq_dev.shape[1]
+        n, stride = self._call_shape(iq_dev, torch.complex64)
         self._grow_for(n)
-        stride = iq_dev.stride(0) if self.n_channels > 1 else n
         if disc_out is not None:
             assert disc_out.dtype == torch.float32 and disc_out.is_cuda and disc_out.shape[0] == self.n_channels
             assert disc_out.stride(1) == 1 and (self.n_channels == 1 or disc_out.stride(0) == stride)
@@ -173,10 +151,8 @@ class DiscriminatorBank(_lib.Handle):
         if x.shape[1] == 0:
             return [np.array([], dtype=np.uint8) if active is None or active[k] else None for k in range(self.n_channels)]
         d, cnt = self.demodulate_device(self._torch.from_numpy(x).cuda(), active)
-        cnt = cnt.cpu().numpy()
-        m = int(cnt.max())
-        d = d[:, :m].cpu().numpy()
-        return [d[k, :cnt[k]].copy() if active is None or active[k] else None for k in range(self.n_channels)]
+        dib = self._to_host(cnt, d)[0]
+        return [dib[k] if active is None or active[k] else None for k in range(self.n_channels)]
 
 
 class DiscriminatorDemodulator:
