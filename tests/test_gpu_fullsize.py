@@ -200,3 +200,42 @@ def test_plan_keeps_bits_and_history():
     assert np.array_equal(a.arm_history, hist)
     ya, yb = a.process_device(x), b.process_device(x)
     assert torch.equal(ya, yb) and np.array_equal(a.arm_history, b.arm_history)
+
+
+def test_plan_untimed_calls_and_profiling_state():
+    """plan() on a call that launches no profiled kernel (M = 28: the per-hop kernel only; M = 1024: a call of 8 hops)
+    returns 0 without timing, and leaves the profiling state, the outputs and the carried history as it found them.  On a
+    timed call it leaves profiling on or off as it was."""
+    import torch
+    import wavehip
+
+    g = torch.Generator(device="cuda").manual_seed(78)
+
+    def noise(n):
+        return torch.view_as_complex(torch.randn(n, 2, device="cuda", generator=g).mul_(0.5))
+
+    for fs, bw, n, prof in ((280_000, 10_000, 28 * 40, False), (280_000, 10_000, 28 * 40, True),
+                            (10_000_000, 9765, 1024 + 512 * 7, False), (10_000_000, 9765, 1024 + 512 * 7, True)):
+        a, b = wavehip.PolyphaseChannelizer(fs, bw), wavehip.PolyphaseChannelizer(fs, bw)
+        assert a.channel_count in (28, 1024) and a.hops(n) == (79 if a.channel_count == 28 else 8)
+        x = noise(n)
+        a.process_device(x)
+        b.process_device(x)
+        a.profile(prof)
+        hist = a.arm_history
+        assert a.plan(x, candidates=(0, 8)) == 0
+        assert a.planned["hops_per_run_setting"] == 0 and not a.planned["median_ms"]
+        assert a.profiling == prof and np.array_equal(a.arm_history, hist)
+        ya, yb = a.process_device(x), b.process_device(x)
+        assert torch.equal(ya, yb) and np.array_equal(a.arm_history, b.arm_history)
+    x = noise(1 << 18)
+    for prof in (False, True):
+        a = wavehip.PolyphaseChannelizer(10_000_000, 9765)
+        a.profile(prof)
+        assert a.plan(x, candidates=(0, 8), rounds=1) in (0, 8) and a.profiling == prof
+        a.process_device(x)
+        if prof:
+            assert a.last_kernel_ms() > 0
+        else:                                   # switched off again: the call is not recorded
+            with pytest.raises(RuntimeError, match="no profiled launch"):
+                a.last_kernel_ms()

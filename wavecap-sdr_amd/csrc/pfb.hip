@@ -1025,7 +1025,7 @@ __global__ void stats_merge_kernel(const double *g, int R, int M, double *out) {
 }  // namespace
 
 struct wh_pfb {
-    int M, T, log2M;
+    int M, T;
     DevBuf<float> d_arms;       // [M][T] float32
     DevBuf<float2> d_tw;        // [M]
     DevBuf<float2> d_hist[2];
@@ -1042,40 +1042,55 @@ struct wh_pfb {
     int ablate = 0;             // diagnostics build only (WH_PFB_ABLATE)
     int variant = 0;            // wh_pfb_tune(WH_PFB_TUNE_PREFETCH): 1 = register prefetch, 3 = LDS-DMA prefetch, for both formats
     int path = 0;               // wh_pfb_tune(WH_PFB_TUNE_PATH): 0 auto, 1 per-hop kernel only, 2 run kernel, 3 shaped kernel
+    // planned at create: the per-hop and run kernels' arguments that depend on M and T only (radix plans, strides)
+    PfbGenArgs gen{};
+    size_t gen_smem = 0;
+    PfbRunArgs run{};           // when run_ok
     bool run_ok = false;        // M, T fit pfb_run_kernel
     bool mid_ok = false;        // a compile-time-shaped instance exists (pfb_mid.hip)
-    bool prof = false;          // bracket the fused kernel with events (bench roofline)
+    bool prof = false;          // bracket the main kernel of every call with events (bench roofline)
     // profiling events: a ring of the last EVR launches' (begin, end) pairs, so that a caller can time EVERY launch of a
     // run and read the durations afterwards -- without a host synchronisation between launches (wh_pfb_kernel_ms_back)
     static constexpr int EVR = 64;
-    hipEvent_t ev0[EVR] = {}, ev1[EVR] = {};
-    int ev_cur = 0, ev_last = -1, ev_n = 0;
+    Event ev0[EVR], ev1[EVR];
+    int ev_last = -1, ev_n = 0;
     // side stream of the fast path: the head / tail hops (per-hop kernel) and the history update are independent of the fused
-    // kernel and run beside it (fork / join by events on the caller's stream: still enqueue-only, and capturable)
-    hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    int ev_begin() { ev_cur = (ev_last + 1) % EVR; return ev_cur; }
-    void ev_end() { ev_last = ev_cur; if (ev_n < EVR) ++ev_n; }
+    // kernel and run beside it (fork / join by events on the caller's stream: still enqueue-only, and capturable).  Last:
+    // synchronised and destroyed before the buffers go.
+    Event ev_fork, ev_join;
+    Stream side;
 };
 
 extern "C" int wh_pfb_create(wh_pfb **out, int M, int T, const double *h_arms) {
     if (!out || !h_arms || M < 2 || (M & 1) || T < 1 || T > 64) return set_err(WH_E_ARG, "wh_pfb_create: bad M/T");
     if ((size_t)M * 16 > 160 * 1024) return set_err(WH_E_ARG, "wh_pfb_create: M=%d exceeds the LDS-resident limit", M);
-    wh_pfb *p = new wh_pfb();
-    std::unique_ptr<wh_pfb, void (*)(wh_pfb *)> guard(p, wh_pfb_destroy);  // frees partial state on early return
+    auto p = std::make_unique<wh_pfb>();
     p->M = M; p->T = T;
 #ifdef WH_DIAG
     if (const char *e = getenv("WH_PFB_ABLATE")) p->ablate = atoi(e);
 #endif
+    // factor M into radices 4, 2, 3, 5 (mixed-radix Stockham); anything else falls back to the direct DFT (n_radix = 0)
+    PfbGenArgs &g = p->gen;
+    g.M = M; g.T = T;
     int l2 = 0;
     while ((1 << l2) < M) ++l2;
-    p->log2M = ((1 << l2) == M) ? l2 : 0;
-    {
-        int rem = M;
-        while (rem % 2 == 0) rem /= 2;
-        while (rem % 3 == 0) rem /= 3;
-        while (rem % 5 == 0) rem /= 5;
-        p->run_ok = T == RT && M % 4 == 0 && M >= 64 && M <= 512 && M != FM && rem == 1;
+    g.log2M = ((1 << l2) == M) ? l2 : 0;
+    int rem = M, k = 0;
+    for (int r : {4, 2, 3, 5})
+        while (rem % r == 0 && k < 16) { g.radix[k++] = r; rem /= r; }
+    g.n_radix = rem == 1 ? k : 0;
+    for (int i = g.n_radix; i < 16; ++i) g.radix[i] = 1;
+    p->gen_smem = (size_t)M * sizeof(float2) * ((g.log2M || g.n_radix) ? 2 : 1);
+    // the run kernel takes the same plan: its first pass (radix 4, in registers) is the plan's first
+    p->run_ok = T == RT && M % 4 == 0 && M >= 64 && M <= 512 && g.n_radix > 0;
+    if (p->run_ok) {
+        PfbRunArgs &r = p->run;
+        r.M = M; r.n_radix = g.n_radix;
+        for (int i = 0, s = 1; i < 12; s *= r.radix[i++]) {
+            r.radix[i] = g.radix[i];
+            r.stride[i] = s;
+            r.inv_stride[i] = 1.0f / (float)s;
+        }
     }
     p->mid_ok = pfb_mid_supported(M, T);
     std::vector<float> arms((size_t)M * T);
@@ -1090,14 +1105,10 @@ extern "C" int wh_pfb_create(wh_pfb **out, int M, int T, const double *h_arms) {
     WH_HIP(hipGetDevice(&dev));
     WH_HIP(hipGetDeviceProperties(&prop, dev));
     p->cu_count = prop.multiProcessorCount;
-    if (M == FM && T == FT) {
-        if (hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking) != hipSuccess) p->side = nullptr;
-        if (p->side && (hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming) != hipSuccess ||
-                        hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming) != hipSuccess)) {
-            (void)hipStreamDestroy(p->side);
-            p->side = nullptr;
-        }
-    }
+    if (M == FM && T == FT && (p->side.create(hipStreamNonBlocking) != hipSuccess ||
+                               p->ev_fork.create(hipEventDisableTiming) != hipSuccess ||
+                               p->ev_join.create(hipEventDisableTiming) != hipSuccess))
+        p->side.reset();   // the fast path runs without the fork
     WH_HIP(p->d_arms.alloc(arms.size()));
     WH_HIP(p->d_tw.alloc(tw.size()));
     WH_HIP(p->d_hist[0].alloc((size_t)M * T));
@@ -1109,25 +1120,13 @@ extern "C" int wh_pfb_create(wh_pfb **out, int M, int T, const double *h_arms) {
     WH_HIP(hipMemcpy(p->d_tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice));
     WH_HIP(hipMemset(p->d_hist[0], 0, (size_t)M * T * sizeof(float2)));
     WH_HIP(hipMemset(p->d_hist[1], 0, (size_t)M * T * sizeof(float2)));
-    *out = guard.release();
+    g.arms = p->run.arms = p->d_arms;
+    g.tw = p->run.tw = p->d_tw;
+    *out = p.release();
     return WH_OK;
 }
 
-// the device buffers are DevBufs; the side stream and the events are released here
-extern "C" void wh_pfb_destroy(wh_pfb *p) {
-    if (!p) return;
-    for (int i = 0; i < wh_pfb::EVR; ++i) {
-        if (p->ev0[i]) (void)hipEventDestroy(p->ev0[i]);
-        if (p->ev1[i]) (void)hipEventDestroy(p->ev1[i]);
-    }
-    if (p->side) {
-        (void)hipStreamSynchronize(p->side);
-        (void)hipStreamDestroy(p->side);
-        (void)hipEventDestroy(p->ev_fork);
-        (void)hipEventDestroy(p->ev_join);
-    }
-    delete p;
-}
+extern "C" void wh_pfb_destroy(wh_pfb *p) { delete p; }
 
 extern "C" int wh_pfb_tune(wh_pfb *p, int key, int value) {
     if (!p) return set_err(WH_E_ARG, "wh_pfb_tune: null handle");
@@ -1167,8 +1166,8 @@ extern "C" int wh_pfb_profile(wh_pfb *p, int enable) {
     if (!p) return set_err(WH_E_ARG, "wh_pfb_profile: null handle");
     if (enable && !p->ev0[0]) {
         for (int i = 0; i < wh_pfb::EVR; ++i) {
-            WH_HIP(hipEventCreate(&p->ev0[i]));
-            WH_HIP(hipEventCreate(&p->ev1[i]));
+            WH_HIP(p->ev0[i].create(hipEventDefault));
+            WH_HIP(p->ev1[i].create(hipEventDefault));
         }
     }
     p->prof = enable != 0;
@@ -1193,257 +1192,127 @@ extern "C" size_t wh_pfb_hops(const wh_pfb *p, size_t n) {
     return (n - p->M) / (p->M / 2) + 1;
 }
 
-static int launch_generic(wh_pfb *p, const void *d_iq, int fmt, float *d_out, long long hop0, long long n_hops,
-                          hipStream_t st, long long hop0b = 0, long long n_hops_b = 0, long long row_b = -1) {
-    if (n_hops_b < 0) n_hops_b = 0;
-    if (n_hops <= 0 && n_hops_b <= 0) return WH_OK;
-    if (n_hops < 0) n_hops = 0;
-    PfbGenArgs a;
-    a.x = d_iq;
-    a.fmt = fmt;
-    a.hist = p->d_hist[p->cur];
-    a.out = reinterpret_cast<float2 *>(d_out);
-    a.arms = p->d_arms;
-    a.tw = p->d_tw;
-    a.M = p->M; a.T = p->T; a.log2M = p->log2M;
-    a.hop0 = hop0; a.n_hops = n_hops;
+// ---- dispatch: which kernel family serves a call, and one launcher per family -------------------------------------
+// one call: the channel outputs, or (statistics-only mode, out == nullptr) the activity statistics of its hops
+struct PfbCall {
+    const void *x;
+    int fmt;
+    size_t n;
+    long long H;       // hops (> 0)
+    float2 *out;       // [H][M]
+    double *stats;     // statistics-only mode: [M][5]
+    int accumulate;
+    hipStream_t st;
+};
+
+enum class PfbPath { Fused1024, Shaped, Run, PerHop };
+
+// wh_pfb_tune accepts path 2 only when run_ok and path 3 only when mid_ok
+static PfbPath pfb_path(const wh_pfb *p, bool stats) {
+    const bool fused = p->M == FM && p->T == FT;
+    // statistics-only mode (mid_ok): the fused kernel's statistics form under every setting but the shaped kernel
+    if (stats) return fused && p->path != 3 ? PfbPath::Fused1024 : PfbPath::Shaped;
+    if (p->path == 1) return PfbPath::PerHop;
+    if (p->path == 2) return PfbPath::Run;
+    if (p->path == 3) return PfbPath::Shaped;
+    return fused ? PfbPath::Fused1024 : p->mid_ok ? PfbPath::Shaped : p->run_ok ? PfbPath::Run : PfbPath::PerHop;
+}
+
+// launch() bracketed by the next (begin, end) pair of the event ring when profiling is on
+template <class F>
+static int timed(wh_pfb *p, hipStream_t st, F &&launch) {
+    if (!p->prof) return launch();
+    const int i = (p->ev_last + 1) % wh_pfb::EVR;
+    WH_HIP(hipEventRecord(p->ev0[i], st));
+    if (int rc = launch()) return rc;
+    WH_HIP(hipEventRecord(p->ev1[i], st));
+    p->ev_last = i;
+    if (p->ev_n < wh_pfb::EVR) ++p->ev_n;
+    return WH_OK;
+}
+
+// the per-hop kernel over hops [0, n_hops) and, in the same launch, hops [hop0b, hop0b + n_hops_b) written from output
+// row row_b on (-1: row = hop)
+static int launch_per_hop(const wh_pfb *p, const PfbCall &c, float2 *out, long long n_hops, hipStream_t st,
+                          long long hop0b = 0, long long n_hops_b = 0, long long row_b = -1) {
+    PfbGenArgs a = p->gen;
+    a.x = c.x; a.fmt = c.fmt; a.hist = p->d_hist[p->cur]; a.out = out;
     a.hop0b = hop0b; a.n_hops_b = n_hops_b; a.row_b = row_b;
-    // factor M into radices 4, 2, 3, 5 (mixed-radix Stockham); anything else falls back to the direct DFT
-    a.n_radix = 0;
-    {
-        int rem = p->M, k = 0;
-        int rad[16];
-        while (rem % 4 == 0 && k < 16) { rad[k++] = 4; rem /= 4; }
-        while (rem % 2 == 0 && k < 16) { rad[k++] = 2; rem /= 2; }
-        while (rem % 3 == 0 && k < 16) { rad[k++] = 3; rem /= 3; }
-        while (rem % 5 == 0 && k < 16) { rad[k++] = 5; rem /= 5; }
-        if (rem == 1 && k > 0) {
-            a.n_radix = k;
-            for (int i = 0; i < 16; ++i) a.radix[i] = i < k ? rad[i] : 1;
-        } else {
-            for (int i = 0; i < 16; ++i) a.radix[i] = 1;
-        }
-    }
-    size_t smem = (size_t)p->M * sizeof(float2) * ((p->log2M || a.n_radix) ? 2 : 1);
-    if (smem > 64 * 1024) {
+    const size_t smem = p->gen_smem;
+    if (smem > 64 * 1024)
         WH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(pfb_generic_kernel),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-    }
     // block size: small channel counts are latency-bound per workgroup (a few hundred points, barriers between
     // passes), so fewer threads per hop and more hops in flight per CU win
     int bt = p->M <= 512 ? 64 : 256;
     if (n_hops + n_hops_b <= 2LL * p->cu_count) bt = 256;   // a handful of hops (head of a run-kernel call): latency only
-    // grid.x is limited to 2^31-1; chunk very long tails (never happens for the fast path)
+    // grid.x is limited to 2^31-1; chunk very long ranges A (range B comes with a short range A only)
     const long long MAXG = 1 << 30;
-    if (n_hops_b > 0) {   // two short ranges in one launch
-        hipLaunchKernelGGL(pfb_generic_kernel, dim3((unsigned)(n_hops + n_hops_b)), dim3(bt), smem, st, a);
-        WH_LAUNCH_CHECK();
-        return WH_OK;
-    }
     for (long long off = 0; off < n_hops; off += MAXG) {
-        long long cnt = n_hops - off < MAXG ? n_hops - off : MAXG;
-        a.hop0 = hop0 + off;
-        a.n_hops = cnt;
-        hipLaunchKernelGGL(pfb_generic_kernel, dim3((unsigned)cnt), dim3(bt), smem, st, a);
+        a.hop0 = off;
+        a.n_hops = n_hops - off < MAXG ? n_hops - off : MAXG;
+        hipLaunchKernelGGL(pfb_generic_kernel, dim3((unsigned)(a.n_hops + n_hops_b)), dim3(bt), smem, st, a);
         WH_LAUNCH_CHECK();
     }
     return WH_OK;
 }
 
-static int pfb_run_fmt(wh_pfb *p, const void *d_iq, int fmt, size_t n, float *d_out, void *stream);
-
-extern "C" int wh_pfb_run(wh_pfb *p, const float *d_iq, size_t n, float *d_out, void *stream) {
-    return pfb_run_fmt(p, d_iq, 0, n, d_out, stream);
+// the carried history after the call, into d_hist[cur ^ 1] (pfb_call flips cur once the call is complete)
+static int carry_history(const wh_pfb *p, const PfbCall &c, hipStream_t st) {
+    hipLaunchKernelGGL(pfb_hist_kernel, dim3((p->M * p->T + 255) / 256), dim3(256), 0, st, c.x, c.fmt, p->d_hist[p->cur],
+                       p->d_hist[p->cur ^ 1], p->M, p->T, c.H);
+    WH_LAUNCH_CHECK();
+    return WH_OK;
 }
 
-extern "C" int wh_pfb_run_i16(wh_pfb *p, const int16_t *d_iq16, size_t n, float *d_out, void *stream) {
-    return pfb_run_fmt(p, d_iq16, 1, n, d_out, stream);
-}
-
-static int pfb_run_fmt(wh_pfb *p, const void *d_iq, int fmt, size_t n, float *d_out, void *stream) {
-    if (!p) return set_err(WH_E_ARG, "wh_pfb_run: null handle");
-    hipStream_t st = as_stream(stream);
-    long long H = (long long)wh_pfb_hops(p, n);
-    if (H == 0) return WH_OK;
-    if (!d_iq || !d_out) return set_err(WH_E_ARG, "wh_pfb_run: null buffer");
-    int rc;
-    const bool fast = (p->M == FM && p->T == FT) && p->path != 1 && !(p->path == 3 && p->mid_ok);
-    if (!fast && p->mid_ok && (p->path == 0 || p->path == 3)) {
-        // one launch: head hops, runs and the history update (pfb_mid.hip)
-        PfbMidCall c;
-        c.x = d_iq; c.fmt = fmt; c.n = n;
-        c.hist = p->d_hist[p->cur]; c.new_hist = p->d_hist[p->cur ^ 1];
-        c.out = reinterpret_cast<float2 *>(d_out);
-        c.sink = p->d_sink; c.sink_elems = (size_t)p->M;
-        c.arms = p->d_arms; c.tw = p->d_tw;
-        c.H = H; c.cu_count = p->cu_count; c.hops_per_run = p->gpw_override; c.stats_only = 0;
-        c.stats_ws = nullptr; c.stats_out = nullptr; c.stats_accumulate = 0;
-#ifdef WH_DIAG
-        c.stats_only = p->ablate << 8;
-#endif
-        if (p->prof) WH_HIP(hipEventRecord(p->ev0[p->ev_begin()], st));
-        if ((rc = pfb_mid_launch(p->M, p->T, c, st)) != WH_OK) return rc;
-        if (p->prof) {
-            WH_HIP(hipEventRecord(p->ev1[p->ev_cur], st));
-            p->ev_end();
-        }
-        p->cur ^= 1;
+// the run kernel over hops [8, H); the per-hop kernel does the head
+static int launch_run(wh_pfb *p, const PfbCall &c) {
+    PfbRunArgs a = p->run;
+    a.x = c.x; a.out = c.out;
+    a.first_hop = 8; a.end_hop = c.H;
+    a.max_block = (long long)(c.n / (size_t)(p->M / 2)) - 1;
+    const int cpl = p->M <= 256 ? 1 : 2;
+    const int rgh = cpl == 1 ? 2 : 1;   // hops per loop iteration (the two-quad form has no registers for a second one)
+    // runs of up to 64 hops per wave (halo 12 %), but at least ~24 waves per CU when the input allows
+    long long nh = c.H - 8;
+    long long hpw = (nh + (long long)p->cu_count * 24 - 1) / ((long long)p->cu_count * 24);
+    if (hpw < 8) hpw = 8;
+    if (hpw > 64) hpw = 64;
+    if (p->gpw_override > 0) hpw = p->gpw_override;
+    hpw = (hpw + rgh - 1) / rgh * rgh;
+    a.hops_per_wave = (int)hpw;
+    const long long waves = (nh + hpw - 1) / hpw;
+    const unsigned nwg = (unsigned)((waves + 3) / 4);
+    const size_t smem = (size_t)4 * rgh * p->M * sizeof(float2);   // images; twiddles and taps are static LDS
+    auto kern = cpl == 1 ? (c.fmt == 1 ? pfb_run_kernel<1, 1, 2> : pfb_run_kernel<0, 1, 2>)
+                         : (c.fmt == 1 ? pfb_run_kernel<1, 2, 1> : pfb_run_kernel<0, 2, 1>);
+    return timed(p, c.st, [&] {
+        hipLaunchKernelGGL(kern, dim3(nwg), dim3(256), smem, c.st, a);
+        WH_LAUNCH_CHECK();
         return WH_OK;
-    }
-    const bool run = !fast && p->run_ok && p->path != 1;
-    long long head = (fast || run) ? (H < 8 ? H : 8) : H;
-    // long calls of the fast path: the per-hop kernel (head / tail hops: 11 workgroups, ~16 us of dependent passes) and the
-    // history update go to the handle's side stream and run BESIDE the fused kernel instead of before / after it
-    const bool fork = fast && p->side && (H - 8) / GH >= 8LL * p->cu_count;
-    hipStream_t sg = st;
-    if (fork) {
-        WH_HIP(hipEventRecord(p->ev_fork, st));
-        WH_HIP(hipStreamWaitEvent(p->side, p->ev_fork, 0));
-        sg = p->side;
-    }
-    {
-        // head hops (need the carried history) + the <= 3 ragged tail hops of the fast path, one launch
-        long long tail0 = 0, tailn = 0;
-        if (fast && H > 8) {
-            tail0 = 8 + ((H - 8) / GH) * GH;
-            tailn = H - tail0;
-        }
-        if ((rc = launch_generic(p, d_iq, fmt, d_out, 0, head, sg, tail0, tailn)) != WH_OK) return rc;
-    }
-    const int hist_nxt = p->cur ^ 1;
-    if (fork) {
-        hipLaunchKernelGGL(pfb_hist_kernel, dim3((p->M * p->T + 255) / 256), dim3(256), 0, sg, d_iq, fmt, p->d_hist[p->cur],
-                           p->d_hist[hist_nxt], p->M, p->T, H);
-        WH_LAUNCH_CHECK();
-        WH_HIP(hipEventRecord(p->ev_join, sg));
-    }
-    if (run && H > 8) {
-        PfbRunArgs a;
-        a.x = d_iq;
-        a.out = reinterpret_cast<float2 *>(d_out);
-        a.arms = p->d_arms;
-        a.tw = p->d_tw;
-        a.M = p->M;
-        int k = 0, rem = p->M / 4;
-        a.radix[k++] = 4;
-        while (rem % 4 == 0) { a.radix[k++] = 4; rem /= 4; }
-        while (rem % 2 == 0) { a.radix[k++] = 2; rem /= 2; }
-        while (rem % 3 == 0) { a.radix[k++] = 3; rem /= 3; }
-        while (rem % 5 == 0) { a.radix[k++] = 5; rem /= 5; }
-        a.n_radix = k;
-        for (int i = 0, s = 1; i < 12; ++i) {
-            if (i >= k) a.radix[i] = 1;
-            a.stride[i] = s;
-            a.inv_stride[i] = 1.0f / (float)s;
-            if (i < k) s *= a.radix[i];
-        }
-        a.first_hop = 8;
-        a.end_hop = H;
-        a.max_block = (long long)(n / (size_t)(p->M / 2)) - 1;
-        const int cpl = p->M <= 256 ? 1 : 2;
-        const int rgh = cpl == 1 ? 2 : 1;   // hops per loop iteration (the two-quad form has no registers for a second one)
-        // runs of up to 64 hops per wave (halo 12 %), but at least ~24 waves per CU when the input allows
-        long long nh = H - 8;
-        long long hpw = (nh + (long long)p->cu_count * 24 - 1) / ((long long)p->cu_count * 24);
-        if (hpw < 8) hpw = 8;
-        if (hpw > 64) hpw = 64;
-        if (p->gpw_override > 0) hpw = p->gpw_override;
-        hpw = (hpw + rgh - 1) / rgh * rgh;
-        a.hops_per_wave = (int)hpw;
-        const long long waves = (nh + hpw - 1) / hpw;
-        const unsigned nwg = (unsigned)((waves + 3) / 4);
-        const size_t smem = (size_t)4 * rgh * p->M * sizeof(float2);   // images; twiddles and taps are static LDS
-        if (p->prof) WH_HIP(hipEventRecord(p->ev0[p->ev_begin()], st));
-        if (cpl == 1) {
-            if (fmt == 1) hipLaunchKernelGGL((pfb_run_kernel<1, 1, 2>), dim3(nwg), dim3(256), smem, st, a);
-            else hipLaunchKernelGGL((pfb_run_kernel<0, 1, 2>), dim3(nwg), dim3(256), smem, st, a);
-        } else {
-            if (fmt == 1) hipLaunchKernelGGL((pfb_run_kernel<1, 2, 1>), dim3(nwg), dim3(256), smem, st, a);
-            else hipLaunchKernelGGL((pfb_run_kernel<0, 2, 1>), dim3(nwg), dim3(256), smem, st, a);
-        }
-        WH_LAUNCH_CHECK();
-        if (p->prof) {
-            WH_HIP(hipEventRecord(p->ev1[p->ev_cur], st));
-            p->ev_end();
-        }
-    }
-    if (fast && H > 8) {
-        long long n_groups = (H - 8) / GH;
-        if (n_groups > 0) {
-            PfbFastArgs a;
-            a.x = d_iq;
-            a.out = reinterpret_cast<float2 *>(d_out);
-            a.arms = p->d_arms;
-            a.tw1024 = p->d_tw;
-            a.first_hop = 8;
-            a.n_groups = n_groups;
-            // Run length.  Three-workgroups form (default): runs of 20 hops (32 for int16 input; 31-round sweeps: complex64
-            // 1.186 / 1.195 / 1.211 / 1.223 / 1.281 ms at 16 / 20 / 24 / 32 / 48 hops, int16 1.021 / 1.020 / 1.010 / 1.037 / 1.067 at
-            // 20 / 28 / 32 / 40 / 48), neighbouring runs walked in
-            // opposite directions -- the resident workgroups of the chip then sweep one narrow band of addresses, which the
-            // HBM channels serve better than 768 scattered streams, and the 9-block halo of a run is an L2 hit (FETCH_SIZE
-            // 1.08 x the input at 32 hops; 1.28 x when every run walks upwards).  Two-workgroups forms: runs of
-            // 256 hops (halo 3 %).  Either way at least two rounds of resident workgroups when the input allows.
-            const bool w3 = p->variant == 0 || p->variant == 5 || p->variant == 7;
-            int gpw = w3 ? (fmt == 1 ? 8 : 5) : 64;
-            long long nwg = (n_groups + gpw - 1) / gpw;
-            while (gpw > 2 && nwg < (long long)p->cu_count * (w3 ? 6 : 8)) {
-                gpw = w3 ? gpw - 1 : gpw >> 1;
-                nwg = (n_groups + gpw - 1) / gpw;
-            }
-            if (p->gpw_override > 0) {
-                gpw = p->gpw_override;
-                nwg = (n_groups + gpw - 1) / gpw;
-            }
-            a.groups_per_wg = gpw;
-            a.n_wg = (int)nwg;
-            // automatic mapping: short runs in chunks of 16 per XCD (one band of addresses for the whole chip), long runs as
-            // one contiguous range per XCD (what rounds 1-2 measured best at 128-256 hops)
-            a.map_chunk = p->map_chunk != 0 ? p->map_chunk : (gpw <= 16 ? 16 : -2);
-            a.alt_dir = p->alt_dir;
-            if (a.map_chunk > 0) nwg = (nwg + 8LL * a.map_chunk - 1) / (8LL * a.map_chunk) * (8LL * a.map_chunk);
-            a.max_block = (long long)(n / (size_t)FHOP) - 1;
-#ifdef WH_DIAG
-            a.ablate = p->ablate;
-#endif
-            if (p->prof) WH_HIP(hipEventRecord(p->ev0[p->ev_begin()], st));
-            // kernel form (wh_pfb_tune PREFETCH): 0 / 5 = three workgroups per CU with the LDS-DMA prefetch (default, both input
-            // formats), 7 = three per CU with register prefetch, 1 / 3 = the two-workgroup forms of rounds 1-2 (register / DMA)
-            const bool dma = p->variant == 3;
-            if (p->variant == 0 || p->variant == 5 || p->variant == 7) {
-                if (p->variant != 7) {
-                    if (fmt == 1) hipLaunchKernelGGL((pfb1024_kernel<1, true, false, true>), dim3((unsigned)nwg), dim3(256), 0, st, a);
-                    else hipLaunchKernelGGL((pfb1024_kernel<0, true, false, true>), dim3((unsigned)nwg), dim3(256), 0, st, a);
-                } else {
-                    if (fmt == 1) hipLaunchKernelGGL((pfb1024_kernel<1, false, false, true>), dim3((unsigned)nwg), dim3(256), 0, st, a);
-                    else hipLaunchKernelGGL((pfb1024_kernel<0, false, false, true>), dim3((unsigned)nwg), dim3(256), 0, st, a);
-                }
-            } else if (dma) {
-                if (fmt == 1) hipLaunchKernelGGL((pfb1024_kernel<1, true>), dim3((unsigned)nwg), dim3(256), 0, st, a);
-                else hipLaunchKernelGGL((pfb1024_kernel<0, true>), dim3((unsigned)nwg), dim3(256), 0, st, a);
-            } else if (fmt == 1)
-                hipLaunchKernelGGL(pfb1024_kernel<1>, dim3((unsigned)nwg), dim3(256), 0, st, a);
-            else
-                hipLaunchKernelGGL(pfb1024_kernel<0>, dim3((unsigned)nwg), dim3(256), 0, st, a);
-            WH_LAUNCH_CHECK();
-            if (p->prof) {
-                WH_HIP(hipEventRecord(p->ev1[p->ev_cur], st));
-                p->ev_end();
-            }
-        }
-    }
-    // carry the history
-    int nxt = hist_nxt;
-    if (fork) {
-        WH_HIP(hipStreamWaitEvent(st, p->ev_join, 0));   // join: everything of this call is ordered before what follows on st
-    } else {
-        int tot = p->M * p->T;
-        hipLaunchKernelGGL(pfb_hist_kernel, dim3((tot + 255) / 256), dim3(256), 0, st, d_iq, fmt, p->d_hist[p->cur],
-                           p->d_hist[nxt], p->M, p->T, H);
-        WH_LAUNCH_CHECK();
-    }
-    p->cur = nxt;
-    return WH_OK;
+    });
+}
+
+// the per-hop kernel over every hop, or (run) over the head hops and the run kernel over the rest; then the history
+static int run_split(wh_pfb *p, const PfbCall &c, bool run) {
+    int rc;
+    const long long head = run && c.H > 8 ? 8 : c.H;
+    if ((rc = launch_per_hop(p, c, c.out, head, c.st)) != WH_OK) return rc;
+    if (head < c.H && (rc = launch_run(p, c)) != WH_OK) return rc;
+    return carry_history(p, c, c.st);
+}
+
+using FusedKernel = void (*)(PfbFastArgs);
+
+// M = 1024, the fused kernel's form (wh_pfb_tune PREFETCH): 0 / 5 = three workgroups per CU with the LDS-DMA prefetch
+// (default, both input formats), 7 = three per CU with register prefetch, 1 / 3 = the two-workgroup forms of rounds 1-2
+// (register / DMA)
+static FusedKernel fused_kernel(int variant, int fmt) {
+    const bool i16 = fmt == 1;
+    if (variant == 0 || variant == 5) return i16 ? pfb1024_kernel<1, true, false, true> : pfb1024_kernel<0, true, false, true>;
+    if (variant == 7) return i16 ? pfb1024_kernel<1, false, false, true> : pfb1024_kernel<0, false, false, true>;
+    if (variant == 3) return i16 ? pfb1024_kernel<1, true> : pfb1024_kernel<0, true>;
+    return i16 ? pfb1024_kernel<1> : pfb1024_kernel<0>;
 }
 
 // diagnostics: the filterbank's HBM traffic shape (8 B read, 16 B written per sample) with no arithmetic at all --
@@ -1541,89 +1410,173 @@ static int pfb_stats_ws_reserve(wh_pfb *p, size_t rows, hipStream_t st) {
     return WH_OK;
 }
 
+// one launch of the shaped kernel: head hops, runs and the history update (statistics-only: and the reduction)
+static int run_shaped(wh_pfb *p, const PfbCall &c) {
+    PfbMidCall m;
+    m.x = c.x; m.fmt = c.fmt; m.n = c.n;
+    m.hist = p->d_hist[p->cur]; m.new_hist = p->d_hist[p->cur ^ 1];
+    m.out = c.out; m.sink = p->d_sink; m.sink_elems = (size_t)p->M;
+    m.arms = p->d_arms; m.tw = p->d_tw;
+    m.H = c.H; m.cu_count = p->cu_count; m.hops_per_run = p->gpw_override;
+    m.stats_only = !c.out; m.stats_ws = nullptr; m.stats_out = c.stats; m.stats_accumulate = c.accumulate;
+#ifdef WH_DIAG
+    m.ablate = c.out ? p->ablate : 0;
+#endif
+    PfbMidPlan plan;
+    int rc = pfb_mid_plan(p->M, p->T, m, &plan);
+    if (rc != WH_OK) return rc;
+    if (!c.out) {
+        if ((rc = pfb_stats_ws_reserve(p, (size_t)plan.grid, c.st)) != WH_OK) return rc;
+        m.stats_ws = p->d_stats_ws;
+    }
+    return timed(p, c.st, [&] { return pfb_mid_launch(p->M, m, plan, c.st); });
+}
+
+// run length of the fused kernel, in groups of GH hops per workgroup:
+// Three-workgroups form (default): runs of 20 hops (32 for int16 input; 31-round sweeps: complex64 1.186 / 1.195 / 1.211 /
+// 1.223 / 1.281 ms at 16 / 20 / 24 / 32 / 48 hops, int16 1.021 / 1.020 / 1.010 / 1.037 / 1.067 at 20 / 28 / 32 / 40 / 48),
+// neighbouring runs walked in opposite directions -- the resident workgroups of the chip then sweep one narrow band of
+// addresses, which the HBM channels serve better than 768 scattered streams, and the 9-block halo of a run is an L2 hit
+// (FETCH_SIZE 1.08 x the input at 32 hops; 1.28 x when every run walks upwards).  At least two rounds of
+// resident workgroups when the input allows.
+static int fused_gpw_w3(long long n_groups, int fmt, int cu_count) {
+    int gpw = fmt == 1 ? 8 : 5;
+    while (gpw > 2 && (n_groups + gpw - 1) / gpw < (long long)cu_count * 6) --gpw;
+    return gpw;
+}
+
+// Two-workgroups forms: runs of 256 hops (halo 3 %), at least two rounds of resident workgroups when the input allows.
+static int fused_gpw_w2(long long n_groups, int cu_count) {
+    int gpw = 64;
+    while (gpw > 2 && (n_groups + gpw - 1) / gpw < (long long)cu_count * 8) gpw >>= 1;
+    return gpw;
+}
+
+// Statistics form: nothing is stored, so nothing argues for short runs: one resident round (two workgroups per CU) of equal
+// runs when the call is long enough -- a quarter of the workspace rows for the reduction to read (81 -> ~20 us)
+static int fused_gpw_stats(long long n_groups, int cu_count) {
+    const int gpw = fused_gpw_w2(n_groups, cu_count);
+    return (n_groups + gpw - 1) / gpw > 2LL * cu_count ? (int)((n_groups + 2LL * cu_count - 1) / (2LL * cu_count)) : gpw;
+}
+
+// the fused kernel over groups [0, n_groups) of the hops from 8 on (statistics-only: and the reduction of its rows)
+static int launch_fused(wh_pfb *p, const PfbCall &c, long long n_groups) {
+    const bool stats = !c.out;
+    const bool w3 = p->variant == 0 || p->variant == 5 || p->variant == 7;
+    const int gpw = p->gpw_override > 0 ? p->gpw_override
+                    : stats ? fused_gpw_stats(n_groups, p->cu_count)
+                    : w3    ? fused_gpw_w3(n_groups, c.fmt, p->cu_count)
+                            : fused_gpw_w2(n_groups, p->cu_count);
+    const long long nwg = (n_groups + gpw - 1) / gpw;
+    PfbFastArgs a;
+    a.x = c.x; a.out = c.out; a.arms = p->d_arms; a.tw1024 = p->d_tw;
+    a.first_hop = 8; a.n_groups = n_groups;
+    a.groups_per_wg = gpw; a.n_wg = (int)nwg;
+    // automatic mapping: short runs in chunks of 16 per XCD (one band of addresses for the whole chip), long runs as one
+    // contiguous range per XCD (what rounds 1-2 measured best at 128-256 hops)
+    a.map_chunk = stats ? -2 : p->map_chunk != 0 ? p->map_chunk : (gpw <= 16 ? 16 : -2);
+    a.alt_dir = stats ? 0 : p->alt_dir;
+    a.max_block = (long long)(c.n / (size_t)FHOP) - 1;
+    a.stats_ws = nullptr;
+#ifdef WH_DIAG
+    a.ablate = stats ? 0 : p->ablate;
+#endif
+    long long grid = nwg;
+    if (a.map_chunk > 0) grid = (grid + 8LL * a.map_chunk - 1) / (8LL * a.map_chunk) * (8LL * a.map_chunk);
+    int rc;
+    if (stats) {
+        if ((rc = pfb_stats_ws_reserve(p, (size_t)nwg, c.st)) != WH_OK) return rc;
+        a.stats_ws = p->d_stats_ws;
+    }
+    // the statistics form: two workgroups per CU, the DMA prefetch for int16 input
+    const FusedKernel kern = !stats ? fused_kernel(p->variant, c.fmt)
+                                    : c.fmt == 1 ? pfb1024_kernel<1, true, true> : pfb1024_kernel<0, false, true>;
+    rc = timed(p, c.st, [&] {
+        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), 0, c.st, a);
+        WH_LAUNCH_CHECK();
+        return WH_OK;
+    });
+    if (rc != WH_OK || !stats) return rc;
+    return pfb_stats_rows_reduce(p->d_stats_ws, (int)nwg, -1, p->M, (double)(n_groups * GH), c.stats, c.accumulate, c.st);
+}
+
+// the per-hop kernel over the head hops [0, 8) (they read the carried history) and the <= 3 ragged tail hops, one launch
+static int fused_edges(const wh_pfb *p, const PfbCall &c, long long n_groups, float2 *out, hipStream_t st, long long row_b) {
+    const long long tail0 = c.H > 8 ? 8 + n_groups * GH : 0;
+    return launch_per_hop(p, c, out, c.H < 8 ? c.H : 8, st, tail0, c.H > 8 ? c.H - tail0 : 0, row_b);
+}
+
+static int run_fused(wh_pfb *p, const PfbCall &c) {
+    int rc;
+    const long long n_groups = c.H > 8 ? (c.H - 8) / GH : 0;
+    if (!c.out) {
+        // statistics form (radix-16 stages; 1.13 ms without its stores against the shaped kernel's 1.36 at 2 workgroups per
+        // CU): the edge hops go to a scratch block whose statistics are merged in
+        int acc = c.accumulate;
+        if (n_groups > 0) {
+            if ((rc = launch_fused(p, c, n_groups)) != WH_OK) return rc;
+            acc = 1;
+        }
+        if ((rc = fused_edges(p, c, n_groups, p->d_edge, c.st, c.H < 8 ? c.H : 8)) != WH_OK) return rc;
+        if ((rc = wh_pfb_channel_stats(p, reinterpret_cast<const float *>(p->d_edge.get()), (size_t)(c.H - n_groups * GH),
+                                       c.stats, acc, c.st)) != WH_OK)
+            return rc;
+        return carry_history(p, c, c.st);
+    }
+    // long calls: the per-hop kernel (head / tail hops: 11 workgroups, ~16 us of dependent passes) and the history update
+    // go to the handle's side stream and run BESIDE the fused kernel instead of before / after it
+    const bool fork = p->side && n_groups >= 8LL * p->cu_count;
+    hipStream_t sg = c.st;
+    if (fork) {
+        WH_HIP(hipEventRecord(p->ev_fork, c.st));
+        WH_HIP(hipStreamWaitEvent(p->side, p->ev_fork, 0));
+        sg = p->side;
+    }
+    if ((rc = fused_edges(p, c, n_groups, c.out, sg, -1)) != WH_OK) return rc;
+    if (fork) {
+        if ((rc = carry_history(p, c, sg)) != WH_OK) return rc;
+        WH_HIP(hipEventRecord(p->ev_join, sg));
+    }
+    if (n_groups > 0 && (rc = launch_fused(p, c, n_groups)) != WH_OK) return rc;
+    if (!fork) return carry_history(p, c, c.st);
+    WH_HIP(hipStreamWaitEvent(c.st, p->ev_join, 0));   // join: everything of this call is ordered before what follows on st
+    return WH_OK;
+}
+
+// the history this call wrote becomes the carried one once every launch of the call is issued
+static int pfb_call(wh_pfb *p, PfbPath path, const PfbCall &c) {
+    const int rc = path == PfbPath::Fused1024 ? run_fused(p, c)
+                   : path == PfbPath::Shaped  ? run_shaped(p, c)
+                                              : run_split(p, c, path == PfbPath::Run);
+    if (rc == WH_OK) p->cur ^= 1;
+    return rc;
+}
+
+static int pfb_run_fmt(wh_pfb *p, const void *d_iq, int fmt, size_t n, float *d_out, void *stream) {
+    if (!p) return set_err(WH_E_ARG, "wh_pfb_run: null handle");
+    const long long H = (long long)wh_pfb_hops(p, n);
+    if (H == 0) return WH_OK;
+    if (!d_iq || !d_out) return set_err(WH_E_ARG, "wh_pfb_run: null buffer");
+    return pfb_call(p, pfb_path(p, false), {d_iq, fmt, n, H, reinterpret_cast<float2 *>(d_out), nullptr, 0, as_stream(stream)});
+}
+
+extern "C" int wh_pfb_run(wh_pfb *p, const float *d_iq, size_t n, float *d_out, void *stream) {
+    return pfb_run_fmt(p, d_iq, 0, n, d_out, stream);
+}
+
+extern "C" int wh_pfb_run_i16(wh_pfb *p, const int16_t *d_iq16, size_t n, float *d_out, void *stream) {
+    return pfb_run_fmt(p, d_iq16, 1, n, d_out, stream);
+}
+
 extern "C" int wh_pfb_run_stats(wh_pfb *p, const void *d_iq, int input_format, size_t n, double *d_stats, int accumulate,
                                 void *stream) {
     if (!p) return set_err(WH_E_ARG, "wh_pfb_run_stats: null handle");
     if (input_format != 0 && input_format != 1) return set_err(WH_E_ARG, "wh_pfb_run_stats: input_format 0 (complex64) / 1 (int16)");
     if (!p->mid_ok) return set_err(WH_E_ARG, "wh_pfb_run_stats: no shaped kernel for M=%d T=%d (run + wh_pfb_channel_stats instead)", p->M, p->T);
-    hipStream_t st = as_stream(stream);
     const long long H = (long long)wh_pfb_hops(p, n);
     if (H == 0) return WH_OK;
     if (!d_iq || !d_stats) return set_err(WH_E_ARG, "wh_pfb_run_stats: null buffer");
-    if (p->M == FM && p->T == FT && p->path != 3 && p->d_edge) {
-        // 1024 channels: the tuned kernel in its statistics-only form (radix-16 stages; 1.13 ms without its stores against
-        // the shaped kernel's 1.36 at 2 workgroups per CU), head / tail hops through the per-hop kernel into a scratch block
-        int rc;
-        const long long n_groups = H > 8 ? (H - 8) / GH : 0;
-        const long long head = H < 8 ? H : 8;
-        const long long tail0 = 8 + n_groups * GH, tailn = H > 8 ? H - tail0 : 0;
-        int acc = accumulate;
-        if (n_groups > 0) {
-            PfbFastArgs a;
-            a.x = d_iq; a.out = nullptr; a.arms = p->d_arms; a.tw1024 = p->d_tw;
-            a.first_hop = 8; a.n_groups = n_groups;
-            int gpw = 64;
-            long long nwg = (n_groups + gpw - 1) / gpw;
-            while (gpw > 2 && nwg < (long long)p->cu_count * 8) { gpw >>= 1; nwg = (n_groups + gpw - 1) / gpw; }
-            // nothing is stored, so nothing argues for short runs: one resident round (two workgroups per CU) of equal runs
-            // when the call is long enough -- a quarter of the workspace rows for the reduction to read (81 -> ~20 us)
-            if (nwg > 2LL * p->cu_count) {
-                nwg = 2LL * p->cu_count;
-                gpw = (int)((n_groups + nwg - 1) / nwg);
-                nwg = (n_groups + gpw - 1) / gpw;
-            }
-            if (p->gpw_override > 0) { gpw = p->gpw_override; nwg = (n_groups + gpw - 1) / gpw; }
-            a.groups_per_wg = gpw; a.n_wg = (int)nwg; a.map_chunk = -2; a.alt_dir = 0;
-            a.max_block = (long long)(n / (size_t)FHOP) - 1;
-#ifdef WH_DIAG
-            a.ablate = 0;
-#endif
-            if ((rc = pfb_stats_ws_reserve(p, (size_t)nwg, st)) != WH_OK) return rc;
-            a.stats_ws = p->d_stats_ws;
-            if (p->prof) WH_HIP(hipEventRecord(p->ev0[p->ev_begin()], st));
-            if (input_format == 1) hipLaunchKernelGGL((pfb1024_kernel<1, true, true>), dim3((unsigned)nwg), dim3(256), 0, st, a);
-            else hipLaunchKernelGGL((pfb1024_kernel<0, false, true>), dim3((unsigned)nwg), dim3(256), 0, st, a);
-            WH_LAUNCH_CHECK();
-            if (p->prof) {
-                WH_HIP(hipEventRecord(p->ev1[p->ev_cur], st));
-                p->ev_end();
-            }
-            if ((rc = pfb_stats_rows_reduce(p->d_stats_ws, (int)nwg, -1, p->M, (double)(n_groups * GH), d_stats, acc, st)) != WH_OK)
-                return rc;
-            acc = 1;
-        }
-        if ((rc = launch_generic(p, d_iq, input_format, reinterpret_cast<float *>(p->d_edge.get()), 0, head, st, tail0, tailn, head)) != WH_OK)
-            return rc;
-        if ((rc = wh_pfb_channel_stats(p, reinterpret_cast<const float *>(p->d_edge.get()), (size_t)(head + tailn), d_stats, acc, stream)) != WH_OK)
-            return rc;
-        int nxt = p->cur ^ 1;
-        int tot = p->M * p->T;
-        hipLaunchKernelGGL(pfb_hist_kernel, dim3((tot + 255) / 256), dim3(256), 0, st, d_iq, input_format, p->d_hist[p->cur],
-                           p->d_hist[nxt], p->M, p->T, H);
-        WH_LAUNCH_CHECK();
-        p->cur = nxt;
-        return WH_OK;
-    }
-    PfbMidCall c;
-    c.x = d_iq; c.fmt = input_format; c.n = n;
-    c.hist = p->d_hist[p->cur]; c.new_hist = p->d_hist[p->cur ^ 1];
-    c.out = nullptr; c.sink = p->d_sink; c.sink_elems = (size_t)p->M;
-    c.arms = p->d_arms; c.tw = p->d_tw;
-    c.H = H; c.cu_count = p->cu_count; c.hops_per_run = p->gpw_override;
-    c.stats_only = 1; c.stats_ws = nullptr; c.stats_out = d_stats; c.stats_accumulate = accumulate;
-    long long grid = 0;
-    int rc = pfb_mid_launch(p->M, p->T, c, st, &grid);
-    if (rc != WH_OK) return rc;
-    if ((rc = pfb_stats_ws_reserve(p, (size_t)grid, st)) != WH_OK) return rc;
-    c.stats_ws = p->d_stats_ws;
-    if (p->prof) WH_HIP(hipEventRecord(p->ev0[p->ev_begin()], st));
-    if ((rc = pfb_mid_launch(p->M, p->T, c, st)) != WH_OK) return rc;
-    if (p->prof) {
-        WH_HIP(hipEventRecord(p->ev1[p->ev_cur], st));
-        p->ev_end();
-    }
-    p->cur ^= 1;
-    return WH_OK;
+    return pfb_call(p, pfb_path(p, true), {d_iq, input_format, n, H, nullptr, d_stats, accumulate, as_stream(stream)});
 }
 
 extern "C" int wh_stats_merge(const double *d_gathered, int n_ranks, int n_channels, double *d_out, void *stream) {

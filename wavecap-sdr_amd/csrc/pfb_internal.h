@@ -19,10 +19,21 @@ struct PfbMidCall {
     long long H;             // hops of this call (> 0)
     int cu_count;
     int hops_per_run;        // 0 = choose; tuning override otherwise
-    int stats_only;          // bit 0: statistics-only mode (no channel outputs are stored)
-    double *stats_ws;        // statistics-only: workspace [workgroups][4][M] (sized from the planned grid)
+    int stats_only;          // statistics-only mode (no channel outputs are stored)
+    double *stats_ws;        // statistics-only: workspace [plan.grid][4][M]
     double *stats_out;       // statistics-only: float64 [M][5] = {sum p, sum p^2, hops, min p, max p}
     int stats_accumulate;    // merge into stats_out instead of overwriting
+#ifdef WH_DIAG
+    int ablate;              // diagnostics build: the kernel's ablation bits (wh_pfb_tune key 4)
+#endif
+};
+
+// launch shape of one call (grid: workgroups, one statistics workspace row each; n_head: workgroups of the head hops),
+// and the compiled instance that launches it
+struct PfbMidPlan {
+    long long grid;
+    int hops_per_run, n_head;
+    int (*launch)(const PfbMidCall &c, const PfbMidPlan &plan, hipStream_t st);
 };
 
 // ---- the activity statistic of a channel (A13; the repo's own definition, consumed by the scanner / classifier as dB
@@ -57,9 +68,10 @@ int pfb_stats_rows_reduce(const double *ws, int rows, int skip, int M, double ho
 
 // true when a compiled instance exists for (M, T)
 bool pfb_mid_supported(int M, int T);
-// one launch: head hops (carried history), the runs, and the history update.  Returns a WH_* status.  With grid_out
-// nothing is launched and the planned grid size is returned (the statistics workspace has one row per workgroup).
-int pfb_mid_launch(int M, int T, const PfbMidCall &c, hipStream_t st, long long *grid_out = nullptr);
+// the launch shape of call c (its x, out, history and statistics buffers are not read).  Returns a WH_* status.
+int pfb_mid_plan(int M, int T, const PfbMidCall &c, PfbMidPlan *plan);
+// one launch of the plan: head hops (carried history), runs, history update (statistics-only: and the reduction)
+int pfb_mid_launch(int M, const PfbMidCall &c, const PfbMidPlan &plan, hipStream_t st);
 // spectrum frames (window -> FFT -> fftshift -> dB) through the shaped passes
 struct SpectrumMidCall {
     const float2 *x;         // samples; frame f starts at x + f * frame_stride

@@ -876,28 +876,53 @@ int g_diag_stamp_wg = 0;
     X(2048, 1, 4, 0, 2, 64, 1, 0, 36, 0, 1) \
     X(4096, 1, 2, 0, 2, 1024, 1, 0, 20, 0, 1)
 
+// the kernel instance of an input format (1 = int16 IQ), output or statistics-only form
 template <class C>
-int mid_launch_t(const PfbMidCall &c, hipStream_t st, long long *grid_out) {
-    constexpr int M = C::M, T = C::T, R = C::R, GH = C::GH, NT = C::NTL, NIMG = C::NIMG;
-    static int wg_per_cu[2] = {0, 0};   // resident workgroups per CU of the two format instances
-    const int f = c.fmt == 1 ? 1 : 0;
-    if (c.stats_only && !C::STATS_OK) return set_err(WH_E_ARG, "wh_pfb_run_stats: no statistics-only form for M=%d", C::M);
-    auto kern = f ? pfb_mid_kernel<C, 1> : pfb_mid_kernel<C, 0>;
-    if (wg_per_cu[f] == 0) {
-        // by registers: the kernel is compiled for WPE waves per SIMD (4 SIMDs per CU); by LDS: 160 KiB per CU
-        hipFuncAttributes fa;
-        WH_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kern)));
-        const int by_waves = 4 * C::WPE / (NT / 64);
-        const int by_lds = (int)((160 * 1024) / (((size_t)fa.sharedSizeBytes + 511) / 512 * 512));
-        const int nb = by_waves < by_lds ? by_waves : by_lds;
-        wg_per_cu[f] = nb > 0 ? nb : 1;
-    }
+auto mid_kernel(int fmt, bool stats) {
+    auto kern = fmt == 1 ? pfb_mid_kernel<C, 1> : pfb_mid_kernel<C, 0>;
+    if constexpr (C::STATS_OK)
+        if (stats) kern = fmt == 1 ? pfb_mid_kernel<C, 1, true> : pfb_mid_kernel<C, 0, true>;
+    return kern;
+}
+
+template <class C>
+int mid_launch_t(const PfbMidCall &c, const PfbMidPlan &pl, hipStream_t st) {
+    constexpr int M = C::M, NT = C::NTL;
     MidArgs a;
     a.x = c.x; a.arms = c.arms; a.tw = c.tw;
     a.hist = reinterpret_cast<const v2f *>(c.hist); a.new_hist = reinterpret_cast<v2f *>(c.new_hist);
     a.out = reinterpret_cast<v2f *>(c.out); a.sink = reinterpret_cast<v2f *>(c.sink);
     a.H = c.H; a.n = (long long)c.n;
     a.max_block = (long long)(c.n / (size_t)(M / 2)) - 1;
+    a.hpr = pl.hops_per_run; a.n_head = pl.n_head; a.stats_ws = c.stats_ws;
+#ifdef WH_DIAG
+    a.ablate = c.ablate;
+    a.stamps = g_diag_stamps;
+    a.stamp_wg = g_diag_stamp_wg;
+#endif
+    if (c.stats_only && (!c.stats_ws || !c.stats_out)) return set_err(WH_E_ARG, "wh_pfb_run_stats: null statistics buffer");
+    hipLaunchKernelGGL(mid_kernel<C>(c.fmt, c.stats_only), dim3((unsigned)pl.grid), dim3(NT), 0, st, a);
+    WH_LAUNCH_CHECK();
+    if (!c.stats_only) return WH_OK;
+    return pfb_stats_rows_reduce(c.stats_ws, (int)pl.grid, pl.n_head, M, (double)c.H, c.stats_out, c.stats_accumulate, st);
+}
+
+template <class C>
+int mid_plan_t(const PfbMidCall &c, PfbMidPlan *pl) {
+    constexpr int T = C::T, R = C::R, GH = C::GH, NT = C::NTL, NIMG = C::NIMG;
+    static int wg_per_cu[2] = {0, 0};   // resident workgroups per CU of the two format instances
+    const int f = c.fmt == 1 ? 1 : 0;
+    if (c.stats_only && !C::STATS_OK) return set_err(WH_E_ARG, "wh_pfb_run_stats: no statistics-only form for M=%d", C::M);
+    if (wg_per_cu[f] == 0) {
+        // by registers: the kernel is compiled for WPE waves per SIMD (4 SIMDs per CU); by LDS: 160 KiB per CU (the output
+        // form's, for both forms)
+        hipFuncAttributes fa;
+        WH_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(mid_kernel<C>(c.fmt, false))));
+        const int by_waves = 4 * C::WPE / (NT / 64);
+        const int by_lds = (int)((160 * 1024) / (((size_t)fa.sharedSizeBytes + 511) / 512 * 512));
+        const int nb = by_waves < by_lds ? by_waves : by_lds;
+        wg_per_cu[f] = nb > 0 ? nb : 1;
+    }
     const long long nh = c.H - (T - 1);   // hops of the runs
     int hpr = GH;
     long long n_main = 0;
@@ -917,35 +942,11 @@ int mid_launch_t(const PfbMidCall &c, hipStream_t st, long long *grid_out) {
         const long long runs = (nh + hpr - 1) / hpr;
         n_main = (runs + R - 1) / R;
     }
-    a.hpr = hpr;
-#ifdef WH_DIAG
-    a.ablate = c.stats_only >> 8;   // diagnostics build: wh_pfb_tune(key 4) rides in the upper bits of stats_only
-    a.stamps = g_diag_stamps;
-    a.stamp_wg = g_diag_stamp_wg;
-#endif
     const long long head_hops = c.H < T - 1 ? c.H : T - 1;
-    a.n_head = (int)((head_hops + NIMG - 1) / NIMG);
-    const long long grid = a.n_head + 1 + n_main;
+    const int n_head = (int)((head_hops + NIMG - 1) / NIMG);
+    const long long grid = n_head + 1 + n_main;
     if (grid > 0x7fffffffLL) return set_err(WH_E_ARG, "wh_pfb_run: input too long for one launch");
-    if (grid_out) {           // plan only: the caller sizes the statistics workspace from it
-        *grid_out = grid;
-        return WH_OK;
-    }
-    a.stats_ws = c.stats_ws;
-    if (c.stats_only & 1) {
-        if constexpr (C::STATS_OK) {
-            if (!c.stats_ws || !c.stats_out) return set_err(WH_E_ARG, "wh_pfb_run_stats: null statistics buffer");
-            auto skern = f ? pfb_mid_kernel<C, 1, true> : pfb_mid_kernel<C, 0, true>;
-            hipLaunchKernelGGL(skern, dim3((unsigned)grid), dim3(NT), 0, st, a);
-            WH_LAUNCH_CHECK();
-            hipLaunchKernelGGL(mid_stats_reduce_kernel, dim3((M + 63) / 64), dim3(64, 16), 0, st, c.stats_ws, (int)grid,
-                               a.n_head, M, (double)c.H, c.stats_out, c.stats_accumulate);
-            WH_LAUNCH_CHECK();
-            return WH_OK;
-        }
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(NT), 0, st, a);
-    WH_LAUNCH_CHECK();
+    *pl = {grid, hpr, n_head, mid_launch_t<C>};
     return WH_OK;
 }
 
@@ -1216,24 +1217,28 @@ bool pfb_mid_supported(int M, int T) {
     return false;
 }
 
-int pfb_mid_launch(int M, int T, const PfbMidCall &c, hipStream_t st, long long *grid_out) {
-    // every store of a hop past the end of the call -- and, in a DIAG build's ablation mode, EVERY store -- lands in the
-    // sink row at [0, M): refuse a launch whose sink is missing or shorter than a row (the two memory-access faults of
-    // round 2 came from a work-in-progress build of exactly that path, DESIGN 3.1b)
-    if (!grid_out && (!c.sink || c.sink_elems < (size_t)M))
-        return set_err(WH_E_ARG, "pfb_mid_launch: sink row missing or shorter than M=%d", M);
-    if (!grid_out && !(c.stats_only & 1) && !c.out) return set_err(WH_E_ARG, "pfb_mid_launch: null output");
+int pfb_mid_plan(int M, int T, const PfbMidCall &c, PfbMidPlan *plan) {
     if (T == 9) {
 #define X(M_, R_, GH_, NWF_, WPE_, PB_, PADN_, IMGX_, TREG_, LSP_, R8_) \
-    if (M == M_) return mid_launch_t<MidCfg<M_, 9, R_, GH_, NWF_, WPE_, PB_, PADN_, IMGX_, TREG_, LSP_, R8_>>(c, st, grid_out);
+    if (M == M_) return mid_plan_t<MidCfg<M_, 9, R_, GH_, NWF_, WPE_, PB_, PADN_, IMGX_, TREG_, LSP_, R8_>>(c, plan);
         WH_MID_CONFIGS(X)
 #undef X
     }
 #define X(M_, T_, R_, GH_, NWF_, WPE_, PB_, PADN_, IMGX_, TREG_, LSP_) \
-    if (M == M_ && T == T_) return mid_launch_t<MidCfg<M_, T_, R_, GH_, NWF_, WPE_, PB_, PADN_, IMGX_, TREG_, LSP_>>(c, st, grid_out);
+    if (M == M_ && T == T_) return mid_plan_t<MidCfg<M_, T_, R_, GH_, NWF_, WPE_, PB_, PADN_, IMGX_, TREG_, LSP_>>(c, plan);
     WH_MID_CONFIGS_T(X)
 #undef X
     return set_err(WH_E_ARG, "pfb_mid_launch: no instance for M=%d T=%d", M, T);
+}
+
+int pfb_mid_launch(int M, const PfbMidCall &c, const PfbMidPlan &plan, hipStream_t st) {
+    // every store of a hop past the end of the call -- and, in a DIAG build's ablation mode, EVERY store -- lands in the
+    // sink row at [0, M): refuse a launch whose sink is missing or shorter than a row (the two memory-access faults of
+    // round 2 came from a work-in-progress build of exactly that path, DESIGN 3.1b)
+    if (!c.sink || c.sink_elems < (size_t)M)
+        return set_err(WH_E_ARG, "pfb_mid_launch: sink row missing or shorter than M=%d", M);
+    if (!c.stats_only && !c.out) return set_err(WH_E_ARG, "pfb_mid_launch: null output");
+    return plan.launch(c, plan, st);
 }
 
 // spectrum frame sizes with a shaped kernel (layouts as the filterbank's at the same size; T = 1: no arms)

@@ -138,6 +138,33 @@ class DevBuf {
     size_t n_ = 0;
 };
 
+// Owning HIP stream or event: move-only, created with flags, released on destruction.  Converts to the raw handle.
+template <class H, hipError_t (*Create)(H *, unsigned), hipError_t (*Destroy)(H)>
+class HipHandle {
+  public:
+    HipHandle() = default;
+    HipHandle(HipHandle &&o) noexcept : h_(std::exchange(o.h_, nullptr)) {}
+    HipHandle &operator=(HipHandle &&o) noexcept { std::swap(h_, o.h_); return *this; }   // the old handle goes with o
+    ~HipHandle() { reset(); }
+
+    // replaces the handle with a new one; on failure the owner is left empty
+    hipError_t create(unsigned flags) {
+        reset();
+        hipError_t e = Create(&h_, flags);
+        if (e != hipSuccess) h_ = nullptr;
+        return e;
+    }
+    void reset() { if (h_) (void)Destroy(h_); h_ = nullptr; }
+    operator H() const { return h_; }
+
+  private:
+    H h_ = nullptr;
+};
+// a stream is synchronised before it is destroyed: work still queued on it may use buffers its owner frees next
+inline hipError_t sync_and_destroy(hipStream_t s) { (void)hipStreamSynchronize(s); return hipStreamDestroy(s); }
+using Stream = HipHandle<hipStream_t, hipStreamCreateWithFlags, sync_and_destroy>;
+using Event = HipHandle<hipEvent_t, hipEventCreateWithFlags, hipEventDestroy>;
+
 // The one rule for growing a handle's workspaces at run time: allocate the new buffers into local DevBufs first (a
 // failure returns with the handle untouched), enqueue any carried copy on the caller's stream, then call this before
 // moving them into the handle.  It waits for the caller's stream (the copies) and then the device: earlier calls, on

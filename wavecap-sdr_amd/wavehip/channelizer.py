@@ -33,6 +33,7 @@ class PolyphaseChannelizer(_lib.Handle):
         self.channel_sample_rate = (sample_rate / self.channel_count) * 2
         self._design_filter()
         self.block_counter = 0
+        self.profiling = False
         self._torch = _lib.require_gpu()
         arms = np.ascontiguousarray(self.arms, dtype=np.float64)
         self._create("wh_pfb", self.channel_count, self.taps_per_channel, _lib.dptr(arms, "f64"))
@@ -119,29 +120,50 @@ class PolyphaseChannelizer(_lib.Handle):
         and resident workgroups; tools/pfb_gpw_sweep.py: one box is fastest at 32 hops, the next at 256).  Every
         candidate is timed on the caller's buffers by HIP events in interleaved rounds; the fastest median is set with
         tune(hops_per_run=...) and returned (0 = the built-in choice).  Outputs and carried history are unaffected (every
-        run length gives the same bits); the history is restored afterwards."""
+        run length gives the same bits); the history and the profiling state are restored afterwards.  A call that
+        launches no profiled kernel (a channel count served by the per-hop kernel only, or a call of 8 hops or fewer) has
+        nothing to time: planning stops after the first call and returns 0."""
         import statistics
 
         M1024 = self.channel_count == 1024 and self.taps_per_channel == 9
         if candidates is None:      # 1024 channels: groups of 4 hops per workgroup; shaped kernels: hops per run
             candidates = (0, 3, 4, 5, 6, 8, 12, 64) if M1024 else (0, 16, 32, 64, 128)
-        hist = self.arm_history
+        hist, profiling = self.arm_history, self.profiling
         times: dict[int, list[float]] = {c: [] for c in candidates}
         self.profile(True)
-        for r in range(rounds + 1):
-            for c in candidates:
-                self.tune(hops_per_run=c)
-                out = self.process_device(samples, out)
-                if r:                                     # the first round warms every variant up
-                    times[c].append(self.last_kernel_ms())
-        best = min(candidates, key=lambda c: statistics.median(times[c]))
-        self.tune(hops_per_run=best)
-        self.arm_history = hist
-        self.planned = {"hops_per_run_setting": best, "median_ms": {int(c): round(statistics.median(t), 4) for c, t in times.items()}}
-        return best
+        try:
+            for r in range(rounds + 1):
+                for c in candidates:
+                    self.tune(hops_per_run=c)
+                    out = self.process_device(samples, out)
+                    if r:                                     # the first round warms every variant up
+                        times[c].append(self.last_kernel_ms())
+                    elif c == candidates[0] and not self._profiled_launches():
+                        self.tune(hops_per_run=0)
+                        self.planned = {"hops_per_run_setting": 0, "median_ms": {}, "untimed": "no profiled launch"}
+                        return 0
+            best = min(candidates, key=lambda c: statistics.median(times[c]))
+            self.tune(hops_per_run=best)
+            self.planned = {"hops_per_run_setting": best, "median_ms": {int(c): round(statistics.median(t), 4) for c, t in times.items()}}
+            return best
+        finally:
+            self.arm_history = hist
+            if not profiling:
+                self.profile(False)
 
     def profile(self, enable: bool = True) -> None:
+        """Time the main kernel of every call (last_kernel_ms); switching it on or off forgets the recorded launches."""
         _lib.check(_lib.lib.wh_pfb_profile(self._h, 1 if enable else 0), "wh_pfb_profile")
+        self.profiling = bool(enable)
+
+    def _profiled_launches(self) -> bool:
+        """True when a profiled launch has been recorded since profiling was switched on."""
+        ms = C.c_float()
+        status = _lib.lib.wh_pfb_kernel_ms_back(self._h, 0, C.byref(ms))
+        if status == -1:                                  # WH_E_ARG: none recorded
+            return False
+        _lib.check(status, "wh_pfb_kernel_ms_back")
+        return True
 
     def last_kernel_ms(self, back: int = 0) -> float:
         """Duration of the main filterbank kernel of the most recent profiled launch (back = 0) or of the launch `back`
