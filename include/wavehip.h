@@ -370,6 +370,13 @@ int wh_cqpsk_bank_run(wh_cqpsk_bank *b, const float *d_iq, size_t n, size_t iq_s
                       double *d_symbols, size_t cap, int32_t *d_counts, void *stream);
 int wh_cqpsk_bank_reserve(wh_cqpsk_bank *b, size_t max_samples_per_call, void *stream);
 int wh_cqpsk_bank_reset(wh_cqpsk_bank *b, void *stream);
+/* The carried loop state of one channel (synchronous; the matched filter's history is not part of it), h_state
+ * double[WH_CQPSK_STATE_LEN]: [0] Costas phase, [1] Costas frequency, [2] timing phase, [3] timing integrator,
+ * [4] previous symbol phase (differential decode), [5..12] the timing loop's 4-entry buffer (re, im per entry),
+ * [13] its index (0..3, the newest entry), [14..15] previous symbol, [16..17] previous decision (re, im). */
+#define WH_CQPSK_STATE_LEN 18
+int wh_cqpsk_bank_get_state(wh_cqpsk_bank *b, int channel, double *h_state, void *stream);
+int wh_cqpsk_bank_set_state(wh_cqpsk_bank *b, int channel, const double *h_state, void *stream);
 void wh_cqpsk_bank_destroy(wh_cqpsk_bank *b);
 
 /* ---- N4: ChannelClassifier.update, channel_classifier.py:100-125 ---------------------------------

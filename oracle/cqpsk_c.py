@@ -31,6 +31,8 @@ def _load():
         lib.cqpsk_ref_demodulate.restype = C.c_int
         lib.cqpsk_ref_demodulate.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
         lib.cqpsk_ref_reset.argtypes = [C.c_void_p]
+        lib.cqpsk_ref_get_state.argtypes = [C.c_void_p, C.c_void_p]
+        lib.cqpsk_ref_set_state.argtypes = [C.c_void_p, C.c_void_p]
         lib.cqpsk_ref_destroy.argtypes = [C.c_void_p]
         lib.gardner_ref_create.restype = C.c_void_p
         lib.gardner_ref_create.argtypes = [C.c_double] * 3
@@ -88,6 +90,25 @@ class CQPSKDemodulatorRef:
 
     def reset(self):
         _lib.cqpsk_ref_reset(self._h)
+
+    def state(self) -> dict:
+        """The loop state in the form of wavehip.CQPSKBank.state()."""
+        v = np.zeros(18, dtype=np.float64)
+        _lib.cqpsk_ref_get_state(self._h, v.ctypes.data)
+        return dict(costas_phase=v[0], costas_freq=v[1], timing_phase=v[2], timing_integrator=v[3], prev_phase=v[4],
+                    buffer=[complex(v[5 + 2 * i], v[6 + 2 * i]) for i in range(4)], buffer_index=int(v[13]),
+                    prev_symbol=complex(v[14], v[15]), prev_decision=complex(v[16], v[17]))
+
+    def set_state(self, s: dict) -> None:
+        v = [s["costas_phase"], s["costas_freq"], s["timing_phase"], s["timing_integrator"], s["prev_phase"]]
+        for z in s["buffer"]:
+            v += [complex(z).real, complex(z).imag]
+        v.append(s["buffer_index"])
+        for k in ("prev_symbol", "prev_decision"):
+            v += [complex(s[k]).real, complex(s[k]).imag]
+        a = np.array(v, dtype=np.float64)
+        assert a.shape == (18,)
+        _lib.cqpsk_ref_set_state(self._h, a.ctypes.data)
 
     def demodulate(self, iq, want_symbols: bool = False):
         x = np.ascontiguousarray(iq, dtype=np.complex64)

@@ -74,6 +74,21 @@ static double interp1(double v0, double v1, double v2, double v3, double mu) {
     return c0 + mu * (c1 + mu * (c2 + mu * c3));
 }
 
+/* the loop state as 18 doubles, the layout of wavehip.h's wh_cqpsk_bank_get_state (the lfilter state is not part of it) */
+void cqpsk_ref_get_state(const cqpsk_ref *s, double *v) {
+    v[0] = s->c_phase; v[1] = s->c_freq; v[2] = s->t_phase; v[3] = s->t_integ; v[4] = s->prev_phase;
+    for (int i = 0; i < 4; ++i) { v[5 + 2 * i] = s->buf[i].re; v[6 + 2 * i] = s->buf[i].im; }
+    v[13] = s->buf_idx;
+    v[14] = s->prev_sym.re; v[15] = s->prev_sym.im; v[16] = s->prev_dec.re; v[17] = s->prev_dec.im;
+}
+
+void cqpsk_ref_set_state(cqpsk_ref *s, const double *v) {
+    s->c_phase = v[0]; s->c_freq = v[1]; s->t_phase = v[2]; s->t_integ = v[3]; s->prev_phase = v[4];
+    for (int i = 0; i < 4; ++i) { s->buf[i].re = v[5 + 2 * i]; s->buf[i].im = v[6 + 2 * i]; }
+    s->buf_idx = (int)v[13] & 3;
+    s->prev_sym.re = v[14]; s->prev_sym.im = v[15]; s->prev_dec.re = v[16]; s->prev_dec.im = v[17];
+}
+
 /* returns number of dibits; symbols (optional) gets the complex symbols */
 int cqpsk_ref_demodulate(cqpsk_ref *s, const float *iq, int n, uint8_t *dibits, double *symbols, int cap) {
     if (n <= 0) return 0;

@@ -145,8 +145,10 @@ def c4fm_iq(
     amp: float = 0.5,
     silence: tuple[int, int] | None = None,
     dibits: np.ndarray | None = None,
+    alpha: float = 0.2,
 ) -> tuple[np.ndarray, np.ndarray]:
-    """RRC-shaped C4FM at complex baseband (deviation: symbol 3 -> 1800 Hz).
+    """RRC-shaped C4FM at complex baseband (deviation: symbol 3 -> 1800 Hz).  ``alpha`` is the RRC roll-off: 0.2 is
+    the P25 pulse, 0.5 the wide pulse of the reference's ``wide_pulse=True`` mode (c4fm.py:2436-2443).
 
     Returns (iq complex64[n], transmitted dibits).  ``silence=(a, b)`` replaces
     samples a..b by noise only (exercises fine-sync loss).  ``dibits`` replaces the
@@ -169,7 +171,7 @@ def c4fm_iq(
         k = k0 + dk
         ok = (k >= 0) & (k < n_sym)
         a = np.where(ok, sym[np.clip(k, 0, n_sym - 1)], 0.0)
-        freq += a * _rrc_pulse(tn - k, 0.2)
+        freq += a * _rrc_pulse(tn - k, alpha)
     # normalise pulse so that the matched RRC pair gives unit symbol amplitude
     freq *= 600.0
     phase = 2 * np.pi * np.cumsum(freq + freq_offset_hz) / fs

@@ -68,6 +68,10 @@ def test_argument_errors_do_not_need_a_gpu():
     assert _lib.lib.wh_lsm_bank_run(None, None, 16, 16, None, None, 16, None, None) == -1
     assert _lib.lib.wh_ddc_bank_run(None, None, 16, None, None, None, 16, None) == -1
     assert _lib.lib.wh_bch_decode(None, None, 1, None, None, None, None) == -1
+    st = (ctypes.c_double * 18)()
+    assert _lib.lib.wh_cqpsk_bank_get_state(None, 0, st, None) == -1
+    assert _lib.lib.wh_cqpsk_bank_set_state(None, 0, st, None) == -1
+    assert b"wh_cqpsk_bank_set_state" in _lib.lib.wh_last_error()
 
 
 def test_product_has_no_oracle_or_cpu_fallback():

@@ -131,3 +131,48 @@ def test_c4fm_oracle_muted_input(golden, atan_mode):
         assert np.array_equal(np.array(counts, dtype=np.int32), g[f"{tag}_counts"]), tag
         assert np.array_equal(np.concatenate(dib), g[f"{tag}_dibits"]), tag
         assert peak_rel_err(np.concatenate(soft), g[f"{tag}_soft"]) <= 1e-5, tag
+
+
+def c4fm_wide_case(g, ci):
+    """Input and call lengths of c4fm_wide case ci (oracle/gen_golden.py gen_c4fm_wide / c4fm_wide_input)."""
+    fs, seed, snr10, foff10 = (int(v) for v in g[f"c{ci}_args"])
+    calls = [int(v) for v in g[f"c{ci}_calls"]]
+    iq, _ = S.c4fm_iq(sum(calls), fs, seed, snr_db=snr10 / 10.0, freq_offset_hz=foff10 / 10.0, alpha=0.5)
+    lo, hi = (int(v) for v in g[f"c{ci}_muted"])
+    if lo >= 0:
+        iq = iq.copy()
+        iq[lo:hi] = 0
+    assert S.sha256(iq) == str(g[f"c{ci}_sha"])
+    return fs, calls, iq
+
+
+def test_wide_pulse_designs_match_reference(golden):
+    """wide_pulse=True (c4fm.py:2436-2443): 10 kHz / 12 kHz low-pass and alpha 0.5 RRC equal the reference's taps; at
+    19.2 kHz the stopband lies past Nyquist and the reference raises -- so does the oracle."""
+    g = golden("c4fm_wide")
+    for fs in (48000, 25000):
+        d = C4FMDemodulatorRef(sample_rate=fs, wide_pulse=True)
+        assert np.array_equal(d.lpf, g[f"lpf_{fs}"]) and np.array_equal(d.rrc, g[f"rrc_{fs}"]), fs
+        assert not np.array_equal(d.lpf, C4FMDemodulatorRef(sample_rate=fs).lpf)
+    assert str(g["raises_19200"]) == "ValueError"
+    with pytest.raises(ValueError):
+        C4FMDemodulatorRef(sample_rate=19200, wide_pulse=True)
+
+
+@pytest.mark.parametrize("atan_mode", [0, 1])
+def test_c4fm_wide_oracle_matches_reference(golden, atan_mode):
+    """c4fm_wide: counts and dibits bit-exact, soft symbols <= 1e-5 peak-relative (as for the narrow pulse)."""
+    g = golden("c4fm_wide")
+    for ci in range(int(g["n_cases"])):
+        fs, calls, iq = c4fm_wide_case(g, ci)
+        assert float(g[f"c{ci}_tx_agree"]) > 0.5, ci          # the reference locks on every case
+        d = C4FMDemodulatorRef(sample_rate=fs, wide_pulse=True, atan_mode=atan_mode)
+        dib, soft, counts, pos = [], [], [], 0
+        for m in calls:
+            a, b = d.demodulate(iq[pos:pos + m])
+            pos += m
+            dib.append(a); soft.append(b); counts.append(len(a))
+        assert np.array_equal(np.array(counts, dtype=np.int32), g[f"c{ci}_counts"]), ci
+        mism = np.flatnonzero(np.concatenate(dib) != g[f"c{ci}_dibits"])
+        assert mism.size == 0, f"case {ci}: {mism.size} dibit mismatches, first at {mism[:5]}"
+        assert peak_rel_err(np.concatenate(soft), g[f"c{ci}_soft"]) <= 1e-5, ci

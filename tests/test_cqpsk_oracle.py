@@ -122,3 +122,19 @@ def test_cqpsk_oracle_muted_stretch(golden):
     parts = [d.demodulate(iq[:13000]), d.demodulate(iq[13000:])]
     assert [len(x) for x in parts] == [int(v) for v in g["muted_counts"]]
     assert np.array_equal(np.concatenate(parts), g["muted_dibits"])
+
+
+def test_cqpsk_oracle_state_hook_and_per_sample_rule():
+    """The oracle's set_state / state round trip, and its timing loop is the reference's per-sample rule: from timing
+    phase 7 - 1 ulp at sps 10 the third sample of a 3-sample call fires (ceil(sps - phase) would say the fourth)."""
+    from oracle.cqpsk_c import CQPSKDemodulatorRef
+
+    r = CQPSKDemodulatorRef(48000, 4800)
+    st = r.state()
+    assert st["timing_phase"] == 0.0 and st["buffer"] == [0j] * 4
+    st = dict(st, timing_phase=float.fromhex("0x1.bffffffffffffp+2"), costas_freq=1e-3, buffer=[1, 2j, -3, 4 + 1j],
+              buffer_index=2, prev_symbol=0.5 - 0.5j, prev_decision=-0.7 + 0.7j, prev_phase=0.25)
+    r.set_state(st)
+    assert r.state() == st
+    x = S.noise_c64(3, 2400)
+    assert len(r.demodulate(x)) == 1

@@ -153,3 +153,124 @@ def test_cqpsk_muted_stretch_vs_oracle(golden):
         got.append(gd)
     # ... and the reference itself
     assert [len(x) for x in got] == [int(v) for v in g["muted_counts"]] and np.array_equal(np.concatenate(got), g["muted_dibits"])
+
+
+# ---- the timing loop's edges.  The reference adds 1.0 to the timing phase per sample and fires when it reaches sps
+# (symbol_timing.py:341-344); k_cq_seq steps ceil(sps - phase) samples at a time and corrects the prediction when the
+# rounded sequential sums reach sps one sample early.  These put a channel into a chosen state (CQPSKBank.set_state and
+# the oracle's set_state) so that such an early fire lands on the last sample of a call or of a 64-sample block.
+
+def _cqpsk_pair(C, fs, sr, phases, n_max=4096):
+    import wavehip
+    from oracle.cqpsk_c import CQPSKDemodulatorRef
+
+    bank = wavehip.CQPSKBank(C, fs, sr, max_samples_per_call=n_max)
+    refs = [CQPSKDemodulatorRef(fs, sr) for _ in range(C)]
+    for c in range(C):
+        st = refs[c].state()
+        st["timing_phase"] = phases[c]
+        refs[c].set_state(st)
+        bank.set_state(c, st)
+        assert bank.state(c) == refs[c].state(), c
+    return bank, refs
+
+
+def _cqpsk_calls_match(bank, refs, x, lens):
+    """x complex64 [C, n] cut into `lens`: per call and channel, counts and dibits equal, symbols within 1e-9."""
+    pos = 0
+    for ln in lens:
+        got = bank.demodulate(x[:, pos:pos + ln], want_symbols=True)
+        for c, r in enumerate(refs):
+            rd, rs = r.demodulate(x[c, pos:pos + ln], want_symbols=True)
+            gd, gs = got[c]
+            assert len(gd) == len(rd), (c, pos, ln, len(gd), len(rd))
+            assert np.array_equal(gd, rd), (c, pos, np.flatnonzero(gd != rd)[:5])
+            if len(rs):
+                assert np.max(np.abs(gs - rs)) <= 1e-9 * max(1.0, np.max(np.abs(rs))), (c, pos)
+        pos += ln
+
+
+@pytest.mark.parametrize("fs,sr,phase_hex,n1,fire", [
+    (48000, 4800, "0x1.bffffffffffffp+2", 3, 2),        # sps 10: phase 7 - 1 ulp; ceil(sps - phase) = 4, the sums fire at 3
+    (41000, 10000, "0x1.0cccccccccccbp+1", 2, 1),       # sps 4.1
+])
+def test_cqpsk_timing_fire_on_last_sample_of_call(fs, sr, phase_hex, n1, fire):
+    """An early fire (by rounding) on the LAST sample of a call: the reference fires there; the symbol must not slip into
+    the next call (where it would be interpolated from the wrong four samples with mu off by 1 / sps).  A long call
+    follows, so the shifted symbol's effect on the loop is seen."""
+    t = float.fromhex(phase_hex)
+    p, s = t, []
+    for i in range(n1):                       # the reference's per-sample rule, spelled out
+        p += 1.0
+        if p >= fs / sr:
+            s.append(i)
+            break
+    assert s == [fire]
+    bank, refs = _cqpsk_pair(1, fs, sr, [t])
+    x = S.noise_c64(n1 + 4000, 2400)[None, :]
+    _cqpsk_calls_match(bank, refs, x, [n1, 4000])
+
+
+def test_cqpsk_timing_fire_on_last_sample_of_block():
+    """sps 64.5 (129 000 / 2 000): the phase below makes ceil(sps - phase) = 65 while the sequential sums reach sps after
+    64 samples -- on sample 63, the last of the first 64-sample block, with more blocks of the same call behind it."""
+    fs, sr = 129000, 2000
+    t = float.fromhex("0x1.fffffffffff7fp-2")
+    assert np.ceil(fs / sr - t) == 65
+    p = t
+    for i in range(64):
+        p += 1.0
+    assert p >= fs / sr                      # the 64th addition fires (sample 63)
+    bank, refs = _cqpsk_pair(1, fs, sr, [t])
+    x = S.noise_c64(300 + 3000, 2401)[None, :]
+    _cqpsk_calls_match(bank, refs, x, [300, 3000])
+
+
+@pytest.mark.parametrize("fs,sr", [(48000, 4800), (41000, 10000), (25000, 4800), (48000, 12000), (129000, 2000)])
+def test_cqpsk_timing_phase_sweep(fs, sr):
+    """585 channels, channel (k, u) starting from timing phase (sps - k) + u ulp(sps - k), k = 1..65, u = -4..4 (585
+    distinct phases): the first symbol comes after about k samples, within rounding of a whole sample.  The first 66+
+    samples arrive in calls of 1-4 samples (so first fires land on call ends), then ragged calls of 1-200 samples of
+    noise; every channel and call against the C oracle started from the same state.  Before the consume-the-rest fix
+    7 channels at sps 10, 2 at 4.1 and 24 at 64.5 fired a sample late; at sps 5.208 and 4 no start phase of this grid
+    fires early by rounding, and those two rates stand as controls."""
+    import math
+
+    sps = fs / sr
+    phases = [(sps - k) + u * math.ulp(sps - k) for k in range(1, 66) for u in range(-4, 5)]
+    assert len(set(phases)) == len(phases)
+    C = len(phases)
+    rng = np.random.default_rng(fs + sr)
+    lens = []
+    while sum(lens) < 66:
+        lens.append(int(rng.integers(1, 5)))
+    while sum(lens) < 2000:
+        lens.append(int(rng.integers(1, 201)))
+    bank, refs = _cqpsk_pair(C, fs, sr, phases, n_max=256)
+    x = np.stack([S.noise_c64(sum(lens), 2500 + c) for c in range(C)])
+    _cqpsk_calls_match(bank, refs, x, lens)
+
+
+def test_cqpsk_state_round_trip():
+    """get_state / set_state round trip: a bank whose state was overwritten and then set back to what get_state read
+    continues the stream bit for bit like a bank that was left alone; bad arguments raise."""
+    import wavehip
+
+    x = S.dqpsk_iq(6000, 48000, 2600, symbol_rate=12000, snr_db=18.0, freq_offset_hz=50.0)[0][None, :]
+    a = wavehip.CQPSKBank(1, 48000, 12000, max_samples_per_call=4096)
+    b = wavehip.CQPSKBank(1, 48000, 12000, max_samples_per_call=4096)
+    a.demodulate(x[:, :3000])
+    b.demodulate(x[:, :3000])
+    st = b.state(0)
+    assert st == a.state(0) and st["buffer_index"] in range(4) and st["timing_integrator"] != 0.0
+    b.set_state(0, dict(st, costas_phase=1.0, timing_phase=0.5, buffer=[0j] * 4, prev_symbol=1j))
+    assert b.state(0)["costas_phase"] == 1.0
+    b.set_state(0, st)
+    assert b.state(0) == st
+    (da, sa), = a.demodulate(x[:, 3000:], want_symbols=True)
+    (db, sb), = b.demodulate(x[:, 3000:], want_symbols=True)
+    assert np.array_equal(da, db) and sa.tobytes() == sb.tobytes()
+    with pytest.raises(RuntimeError):
+        a.set_state(0, dict(st, buffer_index=4))
+    with pytest.raises(RuntimeError):
+        a.state(1)

@@ -136,3 +136,94 @@ def test_lsm_edges():
         for c in range(2):
             assert np.array_equal(da[c], db[c]) and pa[c].tobytes() == pb[c].tobytes(), (lo, c)
     assert small.state(1) == big.state(1) and small.max_samples_per_call >= 4900
+
+
+def test_lsm_monitor_call_sizes_golden_and_oracle(golden):
+    """lsm_big (the monitor's whole-buffer calls: 72 000 samples at 48 kHz, trunking/system.py:1547-1548): a drop-in created
+    for 4 096-sample calls grows mid-stream on its first call; counts and dibits bit-exact against the reference golden,
+    phases within the golden bounds of test_lsm_golden_and_oracle, and dibits, phases and state bit-identical to the C
+    oracle's portable flavour after every call."""
+    import wavehip
+    from oracle.lsm_c import LSMDemodulatorRef
+    from test_lsm_oracle import lsm_big_case
+
+    g = golden("lsm_big")
+    assert int(g["n_cases"]) >= 1
+    for ci in range(int(g["n_cases"])):
+        fs, sr, x, calls = lsm_big_case(g, ci)
+        d = wavehip.LSMDemodulator(fs, sr, max_samples_per_call=4096)
+        r = LSMDemodulatorRef(fs, sr, 1)
+        dib, ph, pos = [], [], 0
+        for ln in calls:
+            o = d.demodulate(x[pos:pos + ln])
+            ro = r.demodulate(x[pos:pos + ln])
+            pos += ln
+            assert np.array_equal(o, ro), (ci, pos)
+            assert d.last_phases.tobytes() == r.last_phases.tobytes(), (ci, pos)
+            sd, sr_ = d.state(), r.state()
+            for k in STATE_KEYS:
+                assert sd[k] == sr_[k], (ci, pos, k, sd[k], sr_[k])
+            dib.append(o)
+            ph.append(d.last_phases)
+        assert d._bank.max_samples_per_call >= max(calls)
+        assert [len(v) for v in dib] == [int(v) for v in g[f"c{ci}_counts"]], ci
+        assert np.array_equal(np.concatenate(dib), g[f"c{ci}_dibits"]), ci
+        dphi = np.abs(np.concatenate(ph).astype(np.float64) - g[f"c{ci}_phases"])
+        dphi = np.minimum(dphi, 2 * np.pi - dphi)
+        assert dphi[:500].max() <= 2e-6 and dphi.max() <= 1e-2, (ci, dphi.max())
+        assert d.state()["clock_is_f32"] == bool(g[f"c{ci}_clock_is_f32"])
+
+
+def test_lsm_bank_8_channels_at_monitor_call_size_bit_identical_to_oracle():
+    """An LSMBank of 8 channels (SNRs 10..24 dB, offsets, one with a muted stretch) in three 72 000-sample calls:
+    every channel's dibits, phases and state equal the C oracle's portable flavour bit for bit."""
+    import wavehip
+    from oracle.lsm_c import LSMDemodulatorRef
+
+    fs, sr, n, C, call = 48000, 4800, 216000, 8, 72000
+    xs = np.stack([S.dqpsk_iq(n, fs, 2700 + c, symbol_rate=sr, snr_db=10.0 + 2 * c,
+                              freq_offset_hz=(c - 4) * 20.0)[0] for c in range(C)])
+    xs[3, 100000:104000] = 0
+    bank = wavehip.LSMBank(C, fs, sr, max_samples_per_call=call)
+    refs = [LSMDemodulatorRef(fs, sr, 1) for _ in range(C)]
+    total = 0
+    for pos in range(0, n, call):
+        dib, ph = bank.demodulate(xs[:, pos:pos + call], want_phases=True)
+        for c in range(C):
+            ro = refs[c].demodulate(xs[c, pos:pos + call])
+            assert np.array_equal(dib[c], ro), (c, pos)
+            assert ph[c].tobytes() == refs[c].last_phases.tobytes(), (c, pos)
+            total += len(ro)
+    for c in range(C):
+        sd, sr_ = bank.state(c), refs[c].state()
+        for k in STATE_KEYS:
+            assert sd[k] == sr_[k], (c, k, sd[k], sr_[k])
+    assert total > 0.9 * C * n / (fs / sr)
+
+
+def test_lsm_25khz_monitor_call_size_bit_identical_to_oracle():
+    """25 kHz (sps 5.208) in 37 500-sample calls (the monitor's 1.5 s buffer at that rate), where no reference golden
+    survives the chaotic horizon (oracle/gen_golden.py gen_lsm_big): 4 channels through a bank created for 8 192-sample
+    calls (it grows on the first call), dibits, phases and state bit-identical to the C oracle's portable flavour."""
+    import wavehip
+    from oracle.lsm_c import LSMDemodulatorRef
+
+    fs, sr, call, C = 25000, 4800, 37500, 4
+    xs = np.stack([S.dqpsk_iq(3 * call, 24000, 2800 + c, symbol_rate=sr, snr_db=14.0 + 4 * c,
+                              freq_offset_hz=-30.0 + 20 * c)[0] for c in range(C)])
+    xs[1, 50000:53000] = 0
+    bank = wavehip.LSMBank(C, fs, sr, max_samples_per_call=8192)
+    refs = [LSMDemodulatorRef(fs, sr, 1) for _ in range(C)]
+    total = 0
+    for pos in range(0, 3 * call, call):
+        dib, ph = bank.demodulate(xs[:, pos:pos + call], want_phases=True)
+        for c in range(C):
+            ro = refs[c].demodulate(xs[c, pos:pos + call])
+            assert np.array_equal(dib[c], ro), (c, pos)
+            assert ph[c].tobytes() == refs[c].last_phases.tobytes(), (c, pos)
+            total += len(ro)
+    for c in range(C):
+        sd, sr_ = bank.state(c), refs[c].state()
+        for k in STATE_KEYS:
+            assert sd[k] == sr_[k], (c, k, sd[k], sr_[k])
+    assert bank.max_samples_per_call >= call and total > 0.9 * C * 3 * call / (fs / sr)

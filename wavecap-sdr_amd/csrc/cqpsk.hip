@@ -245,23 +245,30 @@ __global__ __launch_bounds__(128) void k_cq_seq(CqArgs a) {
             while (true) {
                 double need = ceil(DS(a.sps, s.t_phase));
                 int k = __builtin_amdgcn_readfirstlane((int)fmin(fmax(need, 1.0), 1.0e6));
-                if (j + k > m - 1) {                   // the next symbol lies beyond this block: consume the rest
+                if (j + k > m - 1) {
+                    // the next symbol is predicted beyond this block: consume the rest.  The sequential sums round and
+                    // can reach sps one sample before k says (as below) -- here only on the block's (or call's) last
+                    // sample, which then fires
+                    // (the test is made wave-uniform: a break on a per-lane compare would make the whole loop divergent)
+                    const bool added = j < m - 1;
                     for (int i = j; i < m - 1; ++i) s.t_phase = DA(s.t_phase, 1.0);
-                    break;
-                }
-                double tp = s.t_phase, tprev = tp;
-                for (int i = 0; i < k; ++i) { tprev = tp; tp = DA(tp, 1.0); }
-                if (k > 1 && tprev >= a.sps) { tp = tprev; k -= 1; }          // (rounding of the sequential sums: at most one off)
-                else if (!(tp >= a.sps)) {
-                    if (j + k + 1 > m - 1) {           // the correction step crosses the block end
-                        s.t_phase = tp;
-                        j += k;
-                        continue;
+                    if (!(added && __builtin_amdgcn_readfirstlane((int)(s.t_phase >= a.sps)))) break;
+                    j = m - 1;
+                } else {
+                    double tp = s.t_phase, tprev = tp;
+                    for (int i = 0; i < k; ++i) { tprev = tp; tp = DA(tp, 1.0); }
+                    if (k > 1 && tprev >= a.sps) { tp = tprev; k -= 1; }          // (rounding of the sequential sums: at most one off)
+                    else if (!(tp >= a.sps)) {
+                        if (j + k + 1 > m - 1) {           // the correction step crosses the block end
+                            s.t_phase = tp;
+                            j += k;
+                            continue;
+                        }
+                        tp = DA(tp, 1.0); k += 1;
                     }
-                    tp = DA(tp, 1.0); k += 1;
+                    j += k;
+                    s.t_phase = tp;
                 }
-                j += k;
-                s.t_phase = tp;
                 double2 b0, b1, b2, b3;
                 if (__builtin_expect(j >= 3, 1)) {     // all four samples in this block (all but its first symbol)
                     b0 = make_double2(CQ_RL(crl, j - 3), CQ_RL(cil, j - 3));
@@ -557,6 +564,39 @@ extern "C" int wh_cqpsk_bank_reserve(wh_cqpsk_bank *b, size_t n_max, void *strea
 extern "C" int wh_cqpsk_bank_reset(wh_cqpsk_bank *b, void *stream) {
     if (!b) return set_err(WH_E_ARG, "wh_cqpsk_bank_reset: null handle");
     return cq_reset(b, as_stream(stream));
+}
+
+// The carried loop state of one channel as WH_CQPSK_STATE_LEN doubles (layout in wavehip.h).  Synchronous: not for the
+// hot path (tests put a channel into a chosen state with it).
+extern "C" int wh_cqpsk_bank_get_state(wh_cqpsk_bank *b, int channel, double *h_state, void *stream) {
+    if (!b || !h_state || channel < 0 || channel >= b->C) return set_err(WH_E_ARG, "wh_cqpsk_bank_get_state: bad arguments");
+    hipStream_t st = as_stream(stream);
+    CqState s;
+    WH_HIP(hipMemcpyAsync(&s, b->d_st + channel, sizeof(s), hipMemcpyDeviceToHost, st));
+    WH_HIP(hipStreamSynchronize(st));
+    const double v[WH_CQPSK_STATE_LEN] = {s.c_phase, s.c_freq, s.t_phase, s.t_integ, s.prev_phase,
+                                          s.buf[0].x, s.buf[0].y, s.buf[1].x, s.buf[1].y, s.buf[2].x, s.buf[2].y,
+                                          s.buf[3].x, s.buf[3].y, (double)(s.buf_idx & 3),
+                                          s.prev_sym.x, s.prev_sym.y, s.prev_dec.x, s.prev_dec.y};
+    for (int i = 0; i < WH_CQPSK_STATE_LEN; ++i) h_state[i] = v[i];
+    return WH_OK;
+}
+
+extern "C" int wh_cqpsk_bank_set_state(wh_cqpsk_bank *b, int channel, const double *h_state, void *stream) {
+    if (!b || !h_state || channel < 0 || channel >= b->C || !(h_state[13] >= 0.0 && h_state[13] <= 3.0) ||
+        h_state[13] != (double)(int)h_state[13])
+        return set_err(WH_E_ARG, "wh_cqpsk_bank_set_state: bad arguments (buffer index 0..3)");
+    CqState s;
+    s.c_phase = h_state[0]; s.c_freq = h_state[1]; s.t_phase = h_state[2]; s.t_integ = h_state[3];
+    s.prev_phase = h_state[4];
+    for (int i = 0; i < 4; ++i) s.buf[i] = make_double2(h_state[5 + 2 * i], h_state[6 + 2 * i]);
+    s.buf_idx = (int)h_state[13]; s.pad = 0;
+    s.prev_sym = make_double2(h_state[14], h_state[15]);
+    s.prev_dec = make_double2(h_state[16], h_state[17]);
+    hipStream_t st = as_stream(stream);
+    WH_HIP(hipMemcpyAsync(b->d_st + channel, &s, sizeof(s), hipMemcpyHostToDevice, st));
+    WH_HIP(hipStreamSynchronize(st));       // (s is on this stack frame)
+    return WH_OK;
 }
 
 extern "C" int wh_cqpsk_bank_run(wh_cqpsk_bank *b, const float *d_iq, size_t n, size_t iq_stride, uint8_t *d_dibits,

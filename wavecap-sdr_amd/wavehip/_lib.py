@@ -174,6 +174,8 @@ PROTOTYPES = {
                                   c_void_p]),
     "wh_cqpsk_bank_reserve": (c_int, [c_void_p, c_size_t, c_void_p]),
     "wh_cqpsk_bank_reset": (c_int, [c_void_p, c_void_p]),
+    "wh_cqpsk_bank_get_state": (c_int, [c_void_p, c_int, C.POINTER(c_double), c_void_p]),
+    "wh_cqpsk_bank_set_state": (c_int, [c_void_p, c_int, C.POINTER(c_double), c_void_p]),
     "wh_cqpsk_bank_destroy": (None, [c_void_p]),
     "wh_gardner_bank_create": (c_int, [C.POINTER(c_void_p), c_int, c_double, c_double, c_double]),
     "wh_gardner_bank_run": (c_int, [c_void_p, c_void_p, c_size_t, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p,

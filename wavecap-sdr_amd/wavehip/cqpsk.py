@@ -8,6 +8,7 @@ both algorithms are per-sample feedback loops).  Float64 throughout, like the re
 
 from __future__ import annotations
 
+import ctypes as C
 
 import numpy as np
 from scipy import signal
@@ -41,6 +42,28 @@ def design_rrc_filter_phase2(samples_per_symbol: float, num_taps: int = 65, alph
     return np.asarray(h / np.sqrt(np.sum(h ** 2)), dtype=np.float32)
 
 
+STATE_LEN = 18     # WH_CQPSK_STATE_LEN
+
+
+def state_from_vector(v) -> dict:
+    """wavehip.h's WH_CQPSK_STATE_LEN doubles -> the state dict of CQPSKBank.state()."""
+    return dict(costas_phase=v[0], costas_freq=v[1], timing_phase=v[2], timing_integrator=v[3], prev_phase=v[4],
+                buffer=[complex(v[5 + 2 * i], v[6 + 2 * i]) for i in range(4)], buffer_index=int(v[13]),
+                prev_symbol=complex(v[14], v[15]), prev_decision=complex(v[16], v[17]))
+
+
+def state_to_vector(s: dict) -> list:
+    v = [float(s["costas_phase"]), float(s["costas_freq"]), float(s["timing_phase"]), float(s["timing_integrator"]),
+         float(s["prev_phase"])]
+    for z in s["buffer"]:
+        v += [complex(z).real, complex(z).imag]
+    v.append(float(s["buffer_index"]))
+    for k in ("prev_symbol", "prev_decision"):
+        v += [complex(s[k]).real, complex(s[k]).imag]
+    assert len(v) == STATE_LEN
+    return v
+
+
 class CQPSKBank(_lib.SymbolBank):
     _prefix = "wh_cqpsk_bank"
 
@@ -64,6 +87,20 @@ class CQPSKBank(_lib.SymbolBank):
         self.cap = int(self.max_samples_per_call / (self.samples_per_symbol * 0.5)) + 8
         self._dibits = torch.empty((self.n_channels, self.cap), dtype=torch.uint8, device="cuda")
         self._symbols = None        # complex128 [C, cap], allocated when symbols are first asked for
+
+    def state(self, channel: int = 0) -> dict:
+        """The carried loop state of one channel (the fields of the reference's CostasLoop, MuellerMullerTED and
+        differential decoder; the matched filter's history is not included).  Synchronous."""
+        v = (C.c_double * STATE_LEN)()
+        _lib.check(_lib.lib.wh_cqpsk_bank_get_state(self._h, int(channel), v, _lib.stream_ptr(self._torch)),
+                   "wh_cqpsk_bank_get_state")
+        return state_from_vector(list(v))
+
+    def set_state(self, channel: int, state: dict) -> None:
+        """Put one channel into `state` (a dict as `state()` returns it).  Synchronous."""
+        v = (C.c_double * STATE_LEN)(*state_to_vector(state))
+        _lib.check(_lib.lib.wh_cqpsk_bank_set_state(self._h, int(channel), v, _lib.stream_ptr(self._torch)),
+                   "wh_cqpsk_bank_set_state")
 
     def demodulate_device(self, iq_dev, want_symbols: bool = False):
         torch = self._torch

@@ -109,11 +109,11 @@ class CQPSKDemodulator:
     MMSE_NTAPS = MMSE_NTAPS
     MMSE_NSTEPS = MMSE_NSTEPS
 
-    def __init__(self, sample_rate: int = 19200, symbol_rate: int = 4800) -> None:
+    def __init__(self, sample_rate: int = 19200, symbol_rate: int = 4800, *, max_samples_per_call: int = 1 << 17) -> None:
         self.sample_rate = sample_rate
         self.symbol_rate = symbol_rate
         self.samples_per_symbol = sample_rate / symbol_rate
-        self._bank = LSMBank(1, sample_rate, symbol_rate)
+        self._bank = LSMBank(1, sample_rate, symbol_rate, max_samples_per_call)   # (a longer call grows it)
         self._baseband_taps = self._bank._baseband_taps
         self._mmse_taps = self._bank._mmse_taps
         self.last_phases = np.zeros(0, dtype=np.float32)
