@@ -465,6 +465,28 @@ int wh_gardner_bank_run(wh_gardner_bank *g, const float *d_x, size_t n, size_t s
 int wh_gardner_bank_reset(wh_gardner_bank *g, void *stream);
 void wh_gardner_bank_destroy(wh_gardner_bank *g);
 
+/* ---- P25 channel front, capture.py:2619-2700: freq_shift (capture.py:166-193) then decimate_iq_for_p25
+ * (capture.py:203-295) for n_channels live P25 channels on ONE wideband complex64 chunk, each with its own offset.
+ * The plan follows the sample rate fs (g = gcd(fs, 48000), up = 48000/g, down = fs/g):
+ *   fs <= 48000      pass-through: out = freq_shift(x), rate fs;
+ *   down > 50        subsample: out[j] = freq_shift(x)[j*D], D = fs / 48000, rate fs / D (the phase is computed
+ *                    at the kept samples only);
+ *   otherwise        scipy.signal.resample_poly(., up, down) of both rails, stateless (zero padding at both ends of
+ *                    every call), rate fs*up/down.  h_taps float32[ntaps] = float32(firwin(20 max(up,down) + 1,
+ *                    1/max(up,down), ("kaiser", 5.0))) * up: scipy designs the taps in the input's dtype (float32)
+ *                    and accumulates in float32, oldest sample first; the kernel repeats that order.
+ * create(): h_taps may be NULL only when the plan does not resample.  set_offsets(): h_offsets_hz float64[n_channels],
+ * each rounded half-to-even as Python's round(); 0 = no mix.  out_len(n): samples per channel for a chunk of n.
+ * run(): d_iq complex64[n] (n <= 2^24), h_active optional uint8[n_channels] (0 = row left untouched), d_out
+ * complex64 [n_channels][out_stride], out_stride >= out_len(n).  No workspace: nothing grows, nothing synchronises. */
+typedef struct wh_p25front wh_p25front;
+int wh_p25front_create(wh_p25front **out, int n_channels, int sample_rate, const float *h_taps, int ntaps);
+int wh_p25front_set_offsets(wh_p25front *f, const double *h_offsets_hz);
+size_t wh_p25front_out_len(const wh_p25front *f, size_t n);
+int wh_p25front_run(wh_p25front *f, const float *d_iq, size_t n, const unsigned char *h_active, float *d_out,
+                    size_t out_stride, void *stream);
+void wh_p25front_destroy(wh_p25front *f);
+
 #ifdef __cplusplus
 }
 #endif

@@ -189,6 +189,11 @@ PROTOTYPES = {
     "wh_c4fm_bank_reserve": (c_int, [c_void_p, c_size_t, c_void_p]),
     "wh_c4fm_bank_reset": (c_int, [c_void_p, c_void_p]),
     "wh_c4fm_bank_destroy": (None, [c_void_p]),
+    "wh_p25front_create": (c_int, [C.POINTER(c_void_p), c_int, c_int, C.POINTER(c_float), c_int]),
+    "wh_p25front_set_offsets": (c_int, [c_void_p, C.POINTER(c_double)]),
+    "wh_p25front_out_len": (c_size_t, [c_void_p, c_size_t]),
+    "wh_p25front_run": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "wh_p25front_destroy": (None, [c_void_p]),
 }
 
 for _name, (_res, _args) in PROTOTYPES.items():
