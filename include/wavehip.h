@@ -158,6 +158,7 @@ int wh_chanbank_run_wire(wh_chanbank *b, const void *d_in, size_t n_chunks, floa
  * h_offsets_hz: round(offset_hz) per channel, 0 = no mix; h_squelch_db: NaN = none (bank created with h_squelch_db). */
 int wh_chanbank_set_offsets(wh_chanbank *b, const int *h_offsets_hz, int n_channels, void *stream);
 int wh_chanbank_set_squelch(wh_chanbank *b, const float *h_squelch_db, int n_channels, void *stream);
+/* Device bytes of the workspace a run of n_chunks chunks allocates (grown on the first call that needs it, then kept). */
 size_t wh_chanbank_workspace_bytes(const wh_chanbank *b, size_t n_chunks);
 void wh_chanbank_destroy(wh_chanbank *b);
 

@@ -696,6 +696,14 @@ def test_chain_spectral_noise_reduction(wh, golden):
         record_margin(err[8:-8].max(), TOL, 'interior'); record_margin(err.max(), 1e-3, '8 samples next to a row edge')
         assert err[8:-8].max() <= TOL and err.max() <= 1e-3, (tag, err[8:-8].max(), err.max())
         assert db_close([met["rssi_db"], met["signal_power_db"]], g[f"{tag}_met"]), tag
+    # a call of more than 65535 rows (chunks x channels) is refused
+    import torch
+    cfg = _nbfm_cfg(wh, 0.0)
+    cfg.enable_noise_reduction = True
+    bank = wh.ChannelBank(2_400_000, 1024, [cfg] * 256)
+    x = torch.zeros(257 * 1024, dtype=torch.complex64, device="cuda")
+    with pytest.raises(RuntimeError, match="65535 rows"):
+        bank.process_device(x, 257)
 
 
 def test_n1_squelch_in_bank(wh):

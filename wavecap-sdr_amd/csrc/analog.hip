@@ -1850,49 +1850,357 @@ __global__ __launch_bounds__(256) void rank_select_kernel(const float *rows, int
     }
 }
 
-// Shape of the time-parallel rows: rw waves per workgroup (64 segments each) and rg workgroups per row -- a property of the
-// bank (channel count, chunk length, chain), never of the call, so a bank's numbers do not depend on how many chunks a call
-// carries.  Chains of more than 3 stages keep one wave per row (their state alone is 20 VGPRs per stage).  Banks of one or
-// two channels whose start states come from the impulse response (no warm-up walk per segment) cut the row into 1024
-// segments, two workgroups of 8 waves: such launches are pure latency on an idle chip.
-static void rows_shape(const wh_chanbank_cfg &c, bool fir_start, int *rw_out, int *rg_out) {
-    int rw = c.n_stages > 3 ? 1 : c.n_channels <= 16 ? ROWS_MAXW : c.n_channels <= 64 ? 4 : 1;
-    while (rw > 1 && c.chunk_len < 64 * rw * 16) rw >>= 1;
-    int rg = (fir_start && rw == ROWS_MAXW && c.n_channels <= 2 && c.chunk_len >= 64 * rw * 2 * 16) ? 2 : 1;
-    *rw_out = rw;
-    *rg_out = rg;
+// ---- channel bank: one plan at creation, one launcher per stage ------------------------------------------------------
+// Waves per row of the time-parallel rows forms (64 segments each): a property of the bank (channel count, chunk length),
+// never of the call, so a bank's numbers do not depend on how many chunks a call carries.
+static int row_waves(const wh_chanbank_cfg &c) {
+    int w = c.n_channels <= 16 ? ROWS_MAXW : c.n_channels <= 64 ? 4 : 1;
+    while (w > 1 && c.chunk_len < 64 * w * 16) w >>= 1;
+    return w;
+}
+
+enum class Front { RawDisc, Chan, Sam };   // fm_rawdisc_kernel (fused FM), chan_front_kernel, sam_front_kernel
+enum class RowsForm { None, Sequential, WarmRecurrence, WarmImpulse, Scan };
+enum class Output { FusedFm, RowsFir, Resample, NrCompact, RowsAreAudio };
+
+// What a run of the bank launches, fixed at creation (chanbank_plan).
+struct ChanPlan {
+    Front front = Front::Chan;
+    RowsForm rows = RowsForm::None;
+    int rw = 1, rg = 1, seg = 0;   // waves per workgroup, workgroups per row, segment length (seg 0: one lane per row)
+    int start_ep = 0;              // WarmImpulse: row length of d_G / d_S0, the chain's state count rounded up to even
+    Output out = Output::RowsAreAudio;
+    int TO = 128, fir_phase = 0;   // fused kernel: outputs per tile, the FIR's polyphase register form (fm_fir_phases)
+    size_t smem = 0;               // ... and its dynamic LDS
+    int post = 0;                  // fmbank_finalize_kernel's post
+    bool nr = false;               // spectral noise reduction: STFT frames per row, the shortened row's length
+    int nr_frames = 0, nr_len = 0;
+};
+
+// The fused kernel's dynamic LDS stays under the 64 KiB that need no ceiling of their own.
+static_assert((FM_MAX_TAPS + FM_MAX_SPAN + 1) * sizeof(float) < 64 * 1024, "fused kernel tile above 64 KiB");
+
+// The plan of a bank from its validated configuration.
+//   output: a pure decimation that fits in LDS runs in the fused kernel -- all of plain FM (no IIR stage, no AGC) from
+//           the raw discriminator angles, or the decimating FIR of every other chain's rows -- any other resampler in
+//           resample_kernel; without one the rows (compacted after noise reduction) are the audio.
+//   rows:   the IIR stages and the AGC.  The exact scan form (chan_rows_scan_kernel) for long chunks that the warm-up
+//           form cannot take, and wherever its sequential depth is the shorter one -- the warm-up form walks segment +
+//           warm-up samples per lane, the scan form twice the segment plus the state scans (about 40 sample-equivalents
+//           per stage and scan).  Else the warm-up form where it at least halves the sequential depth (chan_rows_kernel),
+//           its start states from the chain's impulse response (iir_start_kernel) unless the state vector is long or
+//           iir_warmup_form asks for the recurrence warm-up.  Else the sequential recurrence.  Chains of more than 3 stages keep one wave
+//           per row in the warm-up form (their state alone is 20 VGPRs per stage); banks of one or two channels with
+//           impulse-response start states cut the row into 1024 segments, two workgroups of 8 waves: such launches are
+//           pure latency on an idle chip.
+static ChanPlan chanbank_plan(const wh_chanbank_cfg &c) {
+    ChanPlan p;
+    p.post = c.post == 0 ? 0 : (c.agc ? 1 : 2);
+    if (c.noise_reduction && c.chunk_len >= NR_FFT) {   // shorter chunks pass through unchanged (dsp/filters.py:388-389)
+        p.nr = true;
+        p.nr_frames = (c.chunk_len - NR_FFT) / NR_HOP + 1;
+        p.nr_len = (p.nr_frames - 1) * NR_HOP + NR_FFT;
+    }
+    const bool resample = c.ntaps > 0;
+    bool fused_fir = false;
+    if (!p.nr && resample && c.up == 1 && c.ntaps <= FM_MAX_TAPS) {
+        int TO = 256;
+        while (TO > 8 && c.ntaps + (TO - 1) * c.down > FM_MAX_SPAN) TO >>= 1;
+        // the kernel's 86 VGPRs allow 5 workgroups per CU, LDS only 4 at 128 outputs per tile with the reference's
+        // 1001 taps at 50:1 (33.4 KB): a few outputs fewer per tile fit 5, and the launch is occupancy-sensitive (2 / 3 /
+        // 4 workgroups per CU: 4.07 / 2.96 / 2.48 ms).  Measured: 124 outputs (32.6 KB) still runs 4 per CU, 120
+        // (31.8 KB) runs 5: 2.48 -> 2.35 ms; 116 / 112 give the gain back to emptier tiles.
+        auto bytes = [&](int to) {
+            return (size_t)((c.ntaps + 1) & ~1) * sizeof(float) + (size_t)(c.ntaps + 1 + (to - 1) * c.down) * sizeof(float);
+        };
+        if (TO == 128 && (c.down & 1) == 0) {
+            int to = 128;
+            while (to > 100 && bytes(to) > 32000) to -= 4;
+            if (bytes(to) <= 32000) TO = to;
+        }
+        // polyphase register form of the FIR (fm_fir_phases): 21 tap blocks of `down`, 17..32 phase pairs, tiles of 128
+        // outputs, no tap table in LDS (29.7 KB at 1001 taps / 50:1: five workgroups per CU)
+        const bool phase = (c.down & 1) == 0 && c.down >= 34 && c.down <= 64 && c.ntaps <= FIR_Q * c.down &&
+                           c.ntaps + 127 * c.down + 64 <= FM_MAX_SPAN;
+        if (phase) TO = 128;
+        if (c.ntaps + (TO - 1) * c.down <= FM_MAX_SPAN) {
+            fused_fir = true;
+            p.TO = TO;
+            p.fir_phase = phase ? 1 : 0;
+            p.smem = phase ? (size_t)(c.ntaps + (TO - 1) * c.down + 64) * sizeof(float) : bytes(TO);
+        }
+    }
+    if (fused_fir && c.demod == 0 && c.n_stages == 0 && !c.agc && c.post == 0) {
+        p.front = Front::RawDisc;
+        p.out = Output::FusedFm;
+        return p;
+    }
+    p.front = c.demod >= 3 ? Front::Sam : Front::Chan;
+    p.out = fused_fir ? Output::RowsFir : resample ? Output::Resample : p.nr ? Output::NrCompact : Output::RowsAreAudio;
+    if (c.n_stages == 0 && !c.agc) return p;
+
+    const bool warm = !c.agc && c.iir_warmup > 0 && c.n_stages > 0 && (c.chunk_len + 63) / 64 + c.iir_warmup <= c.chunk_len / 2;
+    const int w = row_waves(c), warm_w = c.n_stages > 3 ? 1 : w;
+    if (c.iir_scan && c.chunk_len >= 4096) {
+        const int sg = (c.chunk_len + 64 * w - 1) / (64 * w);
+        const long long depth_warm = (c.chunk_len + 64 * warm_w - 1) / (64 * warm_w) + c.iir_warmup;
+        const long long depth_scan = 2LL * sg + 40LL * (c.n_stages + (c.agc ? 2 : 0)) * (w > 1 ? 2 : 1);
+        if (!warm || depth_scan < depth_warm) {
+            p.rows = RowsForm::Scan; p.rw = w; p.seg = sg;
+            return p;
+        }
+    }
+    if (!warm) {
+        p.rows = RowsForm::Sequential;
+        return p;
+    }
+    int E = 0;
+    for (int i = 0; i < c.n_stages; ++i) E += c.h_stages[i].n - 1;
+    const int EP = (E + 1) & ~1;
+    const bool impulse = c.iir_warmup_form == 0 && E >= 1 && EP <= 16 && c.n_stages <= 3;
+    p.rows = impulse ? RowsForm::WarmImpulse : RowsForm::WarmRecurrence;
+    p.start_ep = impulse ? EP : 0;
+    p.rw = warm_w;
+    p.rg = impulse && warm_w == ROWS_MAXW && c.n_channels <= 2 && c.chunk_len >= 64 * warm_w * 2 * 16 ? 2 : 1;
+    p.seg = (c.chunk_len + 64 * p.rw * p.rg - 1) / (64 * p.rw * p.rg);
+    return p;
+}
+
+// FmArgs of a chain without resampler or tiles (down = TO = R = 1); every pointer and the remaining fields are zero
+static FmArgs fm_args(int fmt, int N, int K, const float *nco_c, int demod, int sample_rate) {
+    FmArgs a{};
+    a.fmt = fmt; a.N = N; a.K = K; a.nco_c = nco_c; a.demod = demod; a.fs_d = (double)sample_rate;
+    a.down = 1; a.TO = 1; a.R = 1;
+    return a;
+}
+
+constexpr int FRONT_PER_BLOCK = 4 * 63 * 16;   // samples of a row per chan_front_kernel workgroup
+
+static unsigned chan_front_blocks(size_t n) { return (unsigned)((n + FRONT_PER_BLOCK - 1) / FRONT_PER_BLOCK); }
+
+using RowsKernel = void (*)(float *, double *, int, int, StageArr, AgcDev, int, int, const double *, int);
+using StartKernel = void (*)(const float *, int, int, int, int, const double *, double *);
+
+// chan_rows_kernel<n_stages> and iir_start_kernel<ep> (ep = 2, 4, .., 16) from tables of their instances
+template <int... I>
+static RowsKernel rows_kernel(int n_stages, std::integer_sequence<int, I...>) {
+    static const RowsKernel k[] = {chan_rows_kernel<I>...};
+    return k[n_stages];
+}
+template <int... I>
+static StartKernel start_kernel(int ep, std::integer_sequence<int, I...>) {
+    static const StartKernel k[] = {iir_start_kernel<2 * (I + 1)>...};
+    return k[ep / 2 - 1];
+}
+static RowsKernel rows_kernel(int n_stages) { return rows_kernel(n_stages, std::make_integer_sequence<int, MAX_STAGES + 1>{}); }
+static StartKernel start_kernel(int ep) { return start_kernel(ep, std::make_integer_sequence<int, 8>{}); }
+
+// The rows kernels' tiles pass 64 KiB at 4 and 8 waves per row.  Their dynamic-LDS ceiling is the largest tile any bank
+// launches them with: every bank sets the same value, so no bank's creation lowers it under another's.
+static int set_rows_lds_ceiling() {
+    const int max_tile = ROWS_MAXW * ROWS_CH * 65 * sizeof(float);
+    for (int ns = 0; ns <= MAX_STAGES; ++ns)
+        WH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(rows_kernel(ns)), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   max_tile));
+    WH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(chan_rows_scan_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               max_tile));
+    return WH_OK;
 }
 
 struct wh_chanbank {
     wh_chanbank_cfg cfg;
+    ChanPlan plan;
+    FmArgs args{};   // every field the configuration fixes; a run sets the call's pointers on a copy
+    AgcDev agc{};
     DevBuf<float> d_nco;
     DevBuf<float> d_squelch;
     std::vector<float> h_stage[2];   // host side of wh_chanbank_set_offsets / _set_squelch (alternating, kept alive)
     int h_stage_cur = 0;
     DevBuf<double> d_taps;
+    DevBuf<float2> d_tphase;   // fir_phase: float2 [21][32] tap pairs (FmArgs::tphase)
     StageArr stages{};
-    DevBuf<ScanPow> d_pow;   // scan form: per-stage state-transition powers for the bank's segment length
-    int scan_seg = 0, scan_w = 1;   // scan form: segment length, waves per row (64 segments each)
-    DevBuf<double> d_G;             // warm-up form: impulse-response states [iir_warmup][start_ep]
-    DevBuf<double> d_S0;            // ... and the segments' start states of a call [rows][segments][start_ep]
-    int start_ep = 0;               // row length of d_G / d_S0: the chain's state count rounded up to even
-    DevBuf<double> d_acc;
-    DevBuf<float> d_fm;
-    DevBuf<float> d_araw;   // fused FM path: raw discriminator angles of the call's chunks [n_chunks][N]
+    DevBuf<ScanPow> d_pow;     // Scan: per-stage state-transition powers for the bank's segment length
+    DevBuf<double> d_G;        // WarmImpulse: impulse-response states [iir_warmup][start_ep]
+    DevBuf<float> d_nr_win;
+    DevBuf<float2> d_nr_tw;
+    // workspace for up to cap_chunks chunks per call (chanbank_workspace)
     size_t cap_chunks = 0;
-    bool fused = false;
-    bool rows_fir = false;   // unfused chain whose resampler is the fused kernel's decimating FIR
-    int fir_phase = 0;       // the FIR's polyphase register form (see fm_fir_phases)
-    DevBuf<float2> d_tphase;
-    int TO = 128;
-    size_t smem = 0;
-    int post = 0;
-    // spectral noise reduction workspace
-    bool nr = false;
-    int nr_frames = 0, nr_len = 0;
-    DevBuf<float> d_nr_win, d_nr_mag, d_nr_sel;
-    DevBuf<float2> d_nr_tw, d_nr_stft;
+    DevBuf<double> d_acc;
+    DevBuf<double> d_S0;       // WarmImpulse: the segments' start states of a call [rows][segments][start_ep]
+    DevBuf<float> d_fm;        // demodulated rows [n_chunks][K][N] before the output stage
+    DevBuf<float> d_araw;      // FusedFm: raw discriminator angles of the call's chunks [n_chunks][N]
+    DevBuf<float2> d_nr_stft;
+    DevBuf<float> d_nr_mag, d_nr_sel;
 };
+
+// Element counts of a bank's workspace for n_chunks chunks: what a run allocates and wh_chanbank_workspace_bytes reports.
+struct ChanWorkspace {
+    size_t acc, S0;                     // double
+    size_t fm, araw, nr_mag, nr_sel;    // float
+    size_t nr_stft;                     // float2
+};
+
+static ChanWorkspace chanbank_workspace(const wh_chanbank *b, size_t n_chunks) {
+    const ChanPlan &p = b->plan;
+    const size_t rows = n_chunks * (size_t)b->cfg.n_channels, N = (size_t)b->cfg.chunk_len;
+    ChanWorkspace w{};
+    w.acc = rows * 2;
+    if (p.rows == RowsForm::WarmImpulse) w.S0 = rows * (size_t)(64 * p.rw * p.rg) * p.start_ep;
+    if (p.out == Output::FusedFm) w.araw = n_chunks * N;
+    else if (p.out != Output::RowsAreAudio) w.fm = rows * N;
+    if (p.nr) {
+        w.nr_stft = w.nr_mag = rows * (size_t)p.nr_frames * NR_BINS;
+        w.nr_sel = rows * NR_BINS * 2;
+    }
+    return w;
+}
+
+// grows the workspace to n_chunks chunks (synchronises; steady state never does)
+static int chanbank_reserve(wh_chanbank *b, size_t n_chunks, hipStream_t st) {
+    if (n_chunks <= b->cap_chunks) return WH_OK;
+    const ChanWorkspace w = chanbank_workspace(b, n_chunks);
+    DevBuf<double> acc, S0;
+    DevBuf<float> fm, araw, nr_mag, nr_sel;
+    DevBuf<float2> nr_stft;
+    // (hipMalloc of 0 bytes allocates nothing: the buffers a plan does not use stay null)
+    WH_HIP(acc.alloc(w.acc)); WH_HIP(S0.alloc(w.S0)); WH_HIP(fm.alloc(w.fm)); WH_HIP(araw.alloc(w.araw));
+    WH_HIP(nr_stft.alloc(w.nr_stft)); WH_HIP(nr_mag.alloc(w.nr_mag)); WH_HIP(nr_sel.alloc(w.nr_sel));
+    WH_HIP(sync_before_swap(st));
+    b->d_acc = std::move(acc); b->d_S0 = std::move(S0); b->d_fm = std::move(fm); b->d_araw = std::move(araw);
+    b->d_nr_stft = std::move(nr_stft); b->d_nr_mag = std::move(nr_mag); b->d_nr_sel = std::move(nr_sel);
+    b->cap_chunks = n_chunks;
+    return WH_OK;
+}
+
+static int launch_front(const wh_chanbank *b, const FmArgs &a, size_t n_chunks, hipStream_t st) {
+    const wh_chanbank_cfg &c = b->cfg;
+    switch (b->plan.front) {
+        case Front::RawDisc: {   // raw discriminator angles + sum |x|^2, once per chunk (shared by the channels)
+            const dim3 grid((unsigned)((c.chunk_len + 4095) / 4096), (unsigned)n_chunks);
+            if (c.input_format == 1) hipLaunchKernelGGL(fm_rawdisc_kernel<1>, grid, dim3(256), 0, st, a, b->d_araw);
+            else hipLaunchKernelGGL(fm_rawdisc_kernel<0>, grid, dim3(256), 0, st, a, b->d_araw);
+            break;
+        }
+        case Front::Chan:
+            hipLaunchKernelGGL(chan_front_kernel, dim3(chan_front_blocks(c.chunk_len), c.n_channels, (unsigned)n_chunks),
+                               dim3(256), 0, st, a);
+            break;
+        case Front::Sam: {
+            const size_t rows = n_chunks * (size_t)c.n_channels;
+            hipLaunchKernelGGL(sam_front_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, a, (int)rows);
+            break;
+        }
+    }
+    WH_LAUNCH_CHECK();
+    return WH_OK;
+}
+
+// start states of all segments, chip-wide (iir_start_kernel)
+static int launch_start_states(const wh_chanbank *b, const float *rows_buf, size_t n_chunks, hipStream_t st) {
+    const ChanPlan &p = b->plan;
+    if (p.rows != RowsForm::WarmImpulse) return WH_OK;
+    const int nseg = 64 * p.rw * p.rg;
+    const dim3 grid((unsigned)(n_chunks * b->cfg.n_channels), (unsigned)((nseg + START_SEGS - 1) / START_SEGS));
+    hipLaunchKernelGGL(start_kernel(p.start_ep), grid, dim3(256), 0, st, rows_buf, b->cfg.chunk_len, p.seg, b->cfg.iir_warmup,
+                       nseg, b->d_G, b->d_S0);
+    WH_LAUNCH_CHECK();
+    return WH_OK;
+}
+
+// the IIR stages and the AGC, in place on the rows
+static int launch_rows(const wh_chanbank *b, float *rows_buf, size_t n_chunks, hipStream_t st) {
+    const wh_chanbank_cfg &c = b->cfg;
+    const ChanPlan &p = b->plan;
+    const size_t rows = n_chunks * (size_t)c.n_channels;
+    const size_t tile_bytes = (size_t)p.rw * ROWS_CH * 65 * sizeof(float);
+    switch (p.rows) {
+        case RowsForm::None: return WH_OK;
+        case RowsForm::Scan:
+            hipLaunchKernelGGL(chan_rows_scan_kernel, dim3((unsigned)rows), dim3(64 * p.rw), tile_bytes, st, rows_buf, b->d_acc,
+                               c.chunk_len, b->stages, c.n_stages, b->agc, p.seg, b->d_pow);
+            break;
+        default: {
+            const dim3 grid(p.seg ? (unsigned)rows : (unsigned)((rows + 63) / 64), (unsigned)p.rg);
+            const double *S0 = p.rows == RowsForm::WarmImpulse ? b->d_S0.get() : nullptr;
+            hipLaunchKernelGGL(rows_kernel(c.n_stages), grid, dim3(64 * p.rw), tile_bytes, st, rows_buf, b->d_acc, (int)rows,
+                               c.chunk_len, b->stages, b->agc, p.seg, c.iir_warmup, S0, p.start_ep);
+            break;
+        }
+    }
+    WH_LAUNCH_CHECK();
+    return WH_OK;
+}
+
+// spectral noise reduction of the rows in d_fm (their first nr_len samples stay)
+static int launch_nr(const wh_chanbank *b, size_t n_chunks, hipStream_t st) {
+    const ChanPlan &p = b->plan;
+    if (!p.nr) return WH_OK;
+    const wh_chanbank_cfg &c = b->cfg;
+    const size_t rows = n_chunks * (size_t)c.n_channels;
+    const int F = p.nr_frames;
+    hipLaunchKernelGGL(nr_stft_kernel, dim3(F, (unsigned)rows), dim3(256), 0, st, b->d_fm, c.chunk_len, F, b->d_nr_win,
+                       b->d_nr_tw, b->d_nr_stft, b->d_nr_mag);
+    WH_LAUNCH_CHECK();
+    const double virt = (double)(F - 1) * 0.1;   // np.percentile(..., 10), method 'linear'
+    int k_lo = (int)floor(virt);
+    int k_hi = k_lo + 1 < F ? k_lo + 1 : F - 1;
+    if (F <= RANK_MAX)
+        hipLaunchKernelGGL(rank_select_kernel, dim3((unsigned)((rows * NR_BINS + 3) / 4)), dim3(256), (size_t)4 * F * sizeof(float),
+                           st, b->d_nr_mag, (int)(rows * NR_BINS), F, k_lo, k_hi, b->d_nr_sel);
+    else
+        hipLaunchKernelGGL(select_kth_kernel, dim3((unsigned)(rows * NR_BINS), 2), dim3(256), 0, st, b->d_nr_mag, F, k_lo, k_hi,
+                           b->d_nr_sel);
+    WH_LAUNCH_CHECK();
+    WH_HIP(hipMemsetAsync(b->d_fm, 0, rows * (size_t)c.chunk_len * sizeof(float), st));
+    hipLaunchKernelGGL(nr_istft_kernel, dim3(F, (unsigned)rows), dim3(256), 0, st, b->d_fm, c.chunk_len, F, b->d_nr_win,
+                       b->d_nr_tw, b->d_nr_stft, b->d_nr_sel, k_lo, (float)(virt - (double)k_lo), c.nr_reduction_linear);
+    WH_LAUNCH_CHECK();
+    hipLaunchKernelGGL(nr_norm_kernel, dim3((unsigned)rows), dim3(256), 0, st, b->d_fm, c.chunk_len, F, b->d_nr_win, b->d_acc);
+    WH_LAUNCH_CHECK();
+    return WH_OK;
+}
+
+// fmbank_fused_kernel over the call's tiles: plain FM (<false>, a.araw set) or the rows' decimating FIR (<true>, a.rows_src)
+static int launch_fused(const wh_chanbank *b, FmArgs a, void (*kern)(FmArgs), size_t n_chunks, hipStream_t st) {
+    const int tiles = (b->cfg.n_out + b->plan.TO - 1) / b->plan.TO;
+    a.R = run_tiles(tiles, n_chunks * (size_t)b->cfg.n_channels);
+    hipLaunchKernelGGL(kern, dim3((tiles + a.R - 1) / a.R, b->cfg.n_channels, (unsigned)n_chunks), dim3(256), b->plan.smem, st, a);
+    WH_LAUNCH_CHECK();
+    return WH_OK;
+}
+
+// the audio: [n_chunks][K][n_out], unscaled until finalize
+static int launch_output(const wh_chanbank *b, FmArgs a, size_t n_chunks, hipStream_t st) {
+    const wh_chanbank_cfg &c = b->cfg;
+    const size_t rows = n_chunks * (size_t)c.n_channels;
+    switch (b->plan.out) {
+        case Output::FusedFm:
+            a.araw = b->d_araw;
+            return launch_fused(b, a, fmbank_fused_kernel<false>, n_chunks, st);
+        case Output::RowsFir:
+            a.rows_src = b->d_fm;
+            return launch_fused(b, a, fmbank_fused_kernel<true>, n_chunks, st);
+        case Output::Resample:
+            return launch_resample(b->d_fm, b->plan.nr ? (size_t)b->plan.nr_len : (size_t)c.chunk_len, (size_t)c.chunk_len, rows,
+                                   a.audio, (size_t)c.n_out, b->d_taps, c.ntaps, c.up, c.down, c.d0, st);
+        case Output::NrCompact:   // compact the shortened rows into the audio buffer
+            WH_HIP(hipMemcpy2DAsync(a.audio, (size_t)c.n_out * sizeof(float), b->d_fm, (size_t)c.chunk_len * sizeof(float),
+                                    (size_t)c.n_out * sizeof(float), rows, hipMemcpyDeviceToDevice, st));
+            return WH_OK;
+        default: return WH_OK;   // RowsAreAudio
+    }
+}
+
+static int launch_finalize(const wh_chanbank *b, float *d_audio, float *d_metrics, int wire_format, void *d_wire,
+                           size_t n_chunks, hipStream_t st) {
+    const wh_chanbank_cfg &c = b->cfg;
+    const ChanPlan &p = b->plan;
+    hipLaunchKernelGGL(fmbank_finalize_kernel, dim3((unsigned)(n_chunks * c.n_channels)), dim3(256), 0, st, d_audio, b->d_acc,
+                       d_metrics, c.chunk_len, p.nr ? p.nr_len : c.chunk_len, c.n_out, p.post, b->d_squelch, c.n_channels,
+                       wire_format, d_wire, p.out == Output::FusedFm ? 1 : 0);
+    WH_LAUNCH_CHECK();
+    return WH_OK;
+}
 
 // Retune without rebuilding the bank (API PATCH of offset_hz -> capture.py:442-501): the mixer constant is one float32
 // per channel in a device array, nothing else in the bank depends on the offsets.  The copy is enqueued on `stream`, so
@@ -1930,36 +2238,34 @@ extern "C" int wh_chanbank_create(wh_chanbank **out, const wh_chanbank_cfg *c) {
     for (int i = 0; i < c->n_stages; ++i)
         if (c->h_stages[i].n < 1 || c->h_stages[i].n > MAX_ORD || c->h_stages[i].a[0] == 0.0)
             return set_err(WH_E_ARG, "wh_chanbank_create: bad IIR stage %d", i);
+    if (c->noise_reduction && (!c->h_nr_window || c->post != 0 || !(c->nr_reduction_linear > 0.0f)))
+        return set_err(WH_E_ARG, "wh_chanbank_create: noise reduction needs the FM chain, a window and a positive factor");
+    const ChanPlan plan = chanbank_plan(*c);
+    {
+        const int n_eff = plan.nr ? plan.nr_len : c->chunk_len;
+        const long long n_up = (long long)n_eff * (resample ? c->up : 1);
+        const long long want = resample ? n_up / c->down + (n_up % c->down ? 1 : 0) : n_eff;
+        if (want != c->n_out) return set_err(WH_E_ARG, "wh_chanbank_create: n_out must be %lld for this configuration", want);
+    }
     std::unique_ptr<wh_chanbank> b(new wh_chanbank());   // frees partial state on early return
     b->cfg = *c;
     b->cfg.h_offsets_hz = nullptr;
     b->cfg.h_taps = nullptr;
     b->cfg.h_stages = nullptr;
-    b->post = c->post == 0 ? 0 : (c->agc ? 1 : 2);
-    if (c->noise_reduction) {
-        if (!c->h_nr_window || c->post != 0 || !(c->nr_reduction_linear > 0.0f))
-            return set_err(WH_E_ARG, "wh_chanbank_create: noise reduction needs the FM chain, a window and a positive factor");
-        if (c->chunk_len >= NR_FFT) {   // shorter chunks pass through unchanged (dsp/filters.py:388-389)
-            b->nr = true;
-            b->nr_frames = (c->chunk_len - NR_FFT) / NR_HOP + 1;
-            b->nr_len = (b->nr_frames - 1) * NR_HOP + NR_FFT;
-            std::vector<float2> tw(NR_FFT);
-            for (int m = 0; m < NR_FFT; ++m) {
-                double ang = -2.0 * M_PI * (double)m / (double)NR_FFT;
-                tw[m] = make_float2((float)cos(ang), (float)sin(ang));
-            }
-            WH_HIP(b->d_nr_win.alloc(NR_FFT));
-            WH_HIP(b->d_nr_tw.alloc(NR_FFT));
-            WH_HIP(hipMemcpy(b->d_nr_win, c->h_nr_window, NR_FFT * sizeof(float), hipMemcpyHostToDevice));
-            WH_HIP(hipMemcpy(b->d_nr_tw, tw.data(), NR_FFT * sizeof(float2), hipMemcpyHostToDevice));
-        }
-    }
     b->cfg.h_nr_window = nullptr;
-    {
-        const int n_eff = b->nr ? b->nr_len : c->chunk_len;
-        const long long n_up = (long long)n_eff * (resample ? c->up : 1);
-        const long long want = resample ? n_up / c->down + (n_up % c->down ? 1 : 0) : n_eff;
-        if (want != c->n_out) return set_err(WH_E_ARG, "wh_chanbank_create: n_out must be %lld for this configuration", want);
+    b->cfg.h_squelch_db = nullptr;
+    b->plan = plan;
+    if (int rc = set_rows_lds_ceiling()) return rc;
+    if (plan.nr) {
+        std::vector<float2> tw(NR_FFT);
+        for (int m = 0; m < NR_FFT; ++m) {
+            double ang = -2.0 * M_PI * (double)m / (double)NR_FFT;
+            tw[m] = make_float2((float)cos(ang), (float)sin(ang));
+        }
+        WH_HIP(b->d_nr_win.alloc(NR_FFT));
+        WH_HIP(b->d_nr_tw.alloc(NR_FFT));
+        WH_HIP(hipMemcpy(b->d_nr_win, c->h_nr_window, NR_FFT * sizeof(float), hipMemcpyHostToDevice));
+        WH_HIP(hipMemcpy(b->d_nr_tw, tw.data(), NR_FFT * sizeof(float2), hipMemcpyHostToDevice));
     }
     std::vector<float> nco(c->n_channels);
     for (int k = 0; k < c->n_channels; ++k) nco[k] = c->h_offsets_hz[k] == 0 ? 0.0f : nco_const(c->h_offsets_hz[k], c->sample_rate);
@@ -1969,134 +2275,69 @@ extern "C" int wh_chanbank_create(wh_chanbank **out, const wh_chanbank_cfg *c) {
         WH_HIP(b->d_squelch.alloc((size_t)c->n_channels));
         WH_HIP(hipMemcpy(b->d_squelch, c->h_squelch_db, (size_t)c->n_channels * sizeof(float), hipMemcpyHostToDevice));
     }
-    b->cfg.h_squelch_db = nullptr;
     if (resample) {
         WH_HIP(b->d_taps.alloc((size_t)c->ntaps));
         WH_HIP(hipMemcpy(b->d_taps, c->h_taps, (size_t)c->ntaps * sizeof(double), hipMemcpyHostToDevice));
     }
-    if (c->n_stages > 0) {
-        // normalise by a[0] in the stage's dtype, as lfilter does on its dtype-cast copies
-        std::vector<StageDev> sd(c->n_stages);
-        for (int i = 0; i < c->n_stages; ++i) {
-            const wh_iir_stage &h = c->h_stages[i];
-            sd[i].is_f64 = h.is_f64;
-            sd[i].n = h.n;
-            for (int k = 0; k < MAX_ORD; ++k) {
-                if (k >= h.n) { sd[i].b[k] = 0.0; sd[i].a[k] = 0.0; continue; }
-                if (h.is_f64) {
-                    sd[i].b[k] = h.b[k] / h.a[0];
-                    sd[i].a[k] = h.a[k] / h.a[0];
-                } else {
-                    sd[i].b[k] = (double)((float)h.b[k] / (float)h.a[0]);
-                    sd[i].a[k] = (double)((float)h.a[k] / (float)h.a[0]);
-                }
+    // normalise by a[0] in the stage's dtype, as lfilter does on its dtype-cast copies
+    for (int i = 0; i < c->n_stages; ++i) {
+        const wh_iir_stage &h = c->h_stages[i];
+        StageDev &s = b->stages.st[i];
+        s.is_f64 = h.is_f64;
+        s.n = h.n;
+        for (int k = 0; k < MAX_ORD; ++k) {
+            if (k >= h.n) { s.b[k] = 0.0; s.a[k] = 0.0; continue; }
+            if (h.is_f64) {
+                s.b[k] = h.b[k] / h.a[0];
+                s.a[k] = h.a[k] / h.a[0];
+            } else {
+                s.b[k] = (double)((float)h.b[k] / (float)h.a[0]);
+                s.a[k] = (double)((float)h.a[k] / (float)h.a[0]);
             }
         }
-        for (int i = 0; i < c->n_stages; ++i) b->stages.st[i] = sd[i];
     }
-    // exact scan form of the rows (see chan_rows_scan_kernel): for long chunks that the warm-up form cannot take, and
-    // wherever its sequential depth is the shorter one -- the warm-up form walks segment + warm-up samples per lane, the
-    // scan form twice the segment plus the state scans (about 40 sample-equivalents per stage and scan).  Waves per row:
-    // a property of the bank (channel count, chunk length), never of the call.
-    if (c->iir_scan && (c->n_stages > 0 || c->agc) && c->chunk_len >= 4096) {
-        int w = c->n_channels <= 16 ? ROWS_MAXW : c->n_channels <= 64 ? 4 : 1;
-        while (w > 1 && c->chunk_len < 64 * w * 16) w >>= 1;
-        const int sg = (c->chunk_len + 64 * w - 1) / (64 * w);
-        long long depth_warm = -1;
-        if (!c->agc && c->iir_warmup > 0 && c->n_stages > 0 && (c->chunk_len + 63) / 64 + c->iir_warmup <= c->chunk_len / 2) {
-            int rw = c->n_stages > 3 ? 1 : w;   // (the warm-up kernel's own wave count, see wh_chanbank_run)
-            depth_warm = (c->chunk_len + 64 * rw - 1) / (64 * rw) + c->iir_warmup;
-        }
-        const long long depth_scan = 2LL * sg + 40LL * (c->n_stages + (c->agc ? 2 : 0)) * (w > 1 ? 2 : 1);
-        if (depth_warm < 0 || depth_scan < depth_warm) {
-            b->scan_seg = sg;
-            b->scan_w = w;
-            AgcDev g;
-            g.on = c->agc; g.target = c->agc_target; g.max_gain = c->agc_max_gain;
-            g.att_b0 = c->agc_att_b0; g.att_a1 = c->agc_att_a1; g.rel_b0 = c->agc_rel_b0; g.rel_a1 = c->agc_rel_a1;
-            // transition powers over one segment and over a wave's 64 segments
-            WH_HIP(b->d_pow.alloc(2));
-            WH_HIP(hipMemset(b->d_pow, 0, 2 * sizeof(ScanPow)));
-            hipLaunchKernelGGL(iir_pow_kernel, dim3(c->n_stages + 1), dim3(MAX_ORD - 1), 0, nullptr, b->stages, c->n_stages, g,
-                               sg, b->d_pow);
+    b->agc = AgcDev{c->agc, c->agc_target, c->agc_max_gain, c->agc_att_b0, c->agc_att_a1, c->agc_rel_b0, c->agc_rel_a1};
+    if (plan.rows == RowsForm::Scan) {   // transition powers over one segment and over a wave's 64 segments
+        WH_HIP(b->d_pow.alloc(2));
+        WH_HIP(hipMemset(b->d_pow, 0, 2 * sizeof(ScanPow)));
+        hipLaunchKernelGGL(iir_pow_kernel, dim3(c->n_stages + 1), dim3(MAX_ORD - 1), 0, nullptr, b->stages, c->n_stages, b->agc,
+                           plan.seg, b->d_pow);
+        WH_LAUNCH_CHECK();
+        if (plan.rw > 1) {
+            hipLaunchKernelGGL(iir_pow_kernel, dim3(c->n_stages + 1), dim3(MAX_ORD - 1), 0, nullptr, b->stages, c->n_stages,
+                               b->agc, 64 * plan.seg, b->d_pow + 1);
             WH_LAUNCH_CHECK();
-            if (w > 1) {
-                hipLaunchKernelGGL(iir_pow_kernel, dim3(c->n_stages + 1), dim3(MAX_ORD - 1), 0, nullptr, b->stages, c->n_stages,
-                                   g, 64 * sg, b->d_pow + 1);
-                WH_LAUNCH_CHECK();
+        }
+        WH_HIP(hipDeviceSynchronize());
+    }
+    if (plan.rows == RowsForm::WarmImpulse) {
+        WH_HIP(b->d_G.alloc((size_t)c->iir_warmup * plan.start_ep));
+        hipLaunchKernelGGL(iir_impulse_kernel, dim3(1), dim3(1), 0, nullptr, b->stages, c->n_stages, c->iir_warmup, plan.start_ep,
+                           b->d_G);
+        WH_LAUNCH_CHECK();
+        WH_HIP(hipDeviceSynchronize());
+    }
+    if (plan.fir_phase) {
+        // tap pairs by block q and phase pair rp: (trev[q down + 2 rp], trev[q down + 2 rp + 1]), trev[i] = h[ntaps - 1 - i]
+        // rounded to float32; zero beyond the filter and for the idle lanes rp >= down / 2
+        std::vector<float2> tp((size_t)FIR_Q * 32, make_float2(0.f, 0.f));
+        for (int q = 0; q < FIR_Q; ++q)
+            for (int rp = 0; rp < c->down / 2; ++rp) {
+                const int i = q * c->down + 2 * rp;
+                tp[(size_t)q * 32 + rp] = make_float2(i < c->ntaps ? (float)c->h_taps[c->ntaps - 1 - i] : 0.f,
+                                                      i + 1 < c->ntaps ? (float)c->h_taps[c->ntaps - 2 - i] : 0.f);
             }
-            WH_HIP(hipDeviceSynchronize());
-            const size_t tile_bytes = (size_t)w * ROWS_CH * 65 * sizeof(float);
-            if (tile_bytes > 64 * 1024)
-                WH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(chan_rows_scan_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_bytes));
-        }
+        WH_HIP(b->d_tphase.alloc(tp.size()));
+        WH_HIP(hipMemcpy(b->d_tphase, tp.data(), tp.size() * sizeof(float2), hipMemcpyHostToDevice));
     }
-    // warm-up form with the start states from the chain's impulse response (see iir_start_kernel)
-    if (!b->scan_seg && c->iir_warmup_form == 0 && !c->agc && c->iir_warmup > 0 && c->n_stages > 0 &&
-        (c->chunk_len + 63) / 64 + c->iir_warmup <= c->chunk_len / 2) {
-        int E = 0;
-        for (int i = 0; i < c->n_stages; ++i) E += b->stages.st[i].n - 1;
-        const int EP = (E + 1) & ~1;
-        if (E >= 1 && EP <= 16 && c->n_stages <= 3) {   // (longer state vectors keep the recurrence warm-up)
-            b->start_ep = EP;
-            WH_HIP(b->d_G.alloc((size_t)c->iir_warmup * EP));
-            hipLaunchKernelGGL(iir_impulse_kernel, dim3(1), dim3(1), 0, nullptr, b->stages, c->n_stages, c->iir_warmup, EP,
-                               b->d_G);
-            WH_LAUNCH_CHECK();
-            WH_HIP(hipDeviceSynchronize());
-        }
-    }
-    // fused path: plain FM (no IIR stage, no AGC), pure decimation, everything fits in LDS.  Every other chain with a pure
-    // decimation that fits uses the same kernel as the decimating FIR of its rows (rows_fir).
-    b->fused = false;
-    const bool plain_fm = c->demod == 0 && c->n_stages == 0 && !c->agc && c->post == 0;
-    if (!b->nr && resample && c->up == 1 && c->ntaps <= FM_MAX_TAPS) {
-        int TO = 256;
-        while (TO > 8 && c->ntaps + (TO - 1) * c->down > FM_MAX_SPAN) TO >>= 1;
-        // the kernel's 86 VGPRs allow 5 workgroups per CU, LDS only 4 at 128 outputs per tile with the reference's
-        // 1001 taps at 50:1 (33.4 KB): a few outputs fewer per tile fit 5, and the launch is occupancy-sensitive (2 / 3 /
-        // 4 workgroups per CU: 4.07 / 2.96 / 2.48 ms).  Measured: 124 outputs (32.6 KB) still runs 4 per CU, 120
-        // (31.8 KB) runs 5: 2.48 -> 2.35 ms; 116 / 112 give the gain back to emptier tiles.
-        if (TO == 128 && (c->down & 1) == 0) {
-            auto bytes = [&](int to) {
-                return (size_t)((c->ntaps + 1) & ~1) * sizeof(float) + (size_t)(c->ntaps + 1 + (to - 1) * c->down) * sizeof(float);
-            };
-            int to = 128;
-            while (to > 100 && bytes(to) > 32000) to -= 4;
-            if (bytes(to) <= 32000) TO = to;
-        }
-        // polyphase register form of the FIR (fm_fir_phases): 21 tap blocks of `down`, 17..32 phase pairs, tiles of 128
-        // outputs, no tap table in LDS (29.7 KB at 1001 taps / 50:1: five workgroups per CU)
-        b->fir_phase = 0;
-        if ((c->down & 1) == 0 && c->down >= 34 && c->down <= 64 && c->ntaps <= FIR_Q * c->down &&
-            c->ntaps + 127 * c->down + 64 <= FM_MAX_SPAN) {
-            b->fir_phase = 1;
-            TO = 128;
-            // tap pairs by block q and phase pair rp: (trev[q down + 2 rp], trev[q down + 2 rp + 1]), trev[i] = h[ntaps - 1 - i]
-            // rounded to float32; zero beyond the filter and for the idle lanes rp >= down / 2
-            std::vector<float2> tp((size_t)FIR_Q * 32, make_float2(0.f, 0.f));
-            for (int q = 0; q < FIR_Q; ++q)
-                for (int rp = 0; rp < c->down / 2; ++rp) {
-                    const int i = q * c->down + 2 * rp;
-                    tp[(size_t)q * 32 + rp] = make_float2(i < c->ntaps ? (float)c->h_taps[c->ntaps - 1 - i] : 0.f,
-                                                          i + 1 < c->ntaps ? (float)c->h_taps[c->ntaps - 2 - i] : 0.f);
-                }
-            WH_HIP(b->d_tphase.alloc(tp.size()));
-            WH_HIP(hipMemcpy(b->d_tphase, tp.data(), tp.size() * sizeof(float2), hipMemcpyHostToDevice));
-        }
-        if (c->ntaps + (TO - 1) * c->down <= FM_MAX_SPAN) {
-            b->fused = plain_fm;
-            b->rows_fir = !plain_fm;
-            b->TO = TO;
-            b->smem = b->fir_phase ? (size_t)(c->ntaps + (TO - 1) * c->down + 64) * sizeof(float)
-                                   : (size_t)((c->ntaps + 1) & ~1) * sizeof(float) + (size_t)(c->ntaps + 1 + (TO - 1) * c->down) * sizeof(float);
-            WH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fmbank_fused_kernel<false>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->smem));
-            WH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fmbank_fused_kernel<true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)b->smem));
-        }
-    }
+    FmArgs &a = b->args;
+    a = fm_args(c->input_format, c->chunk_len, c->n_channels, b->d_nco, c->demod, c->sample_rate);
+    a.skip_fm_sum = plan.out != Output::FusedFm && (c->n_stages > 0 || c->agc) ? 1 : 0;
+    a.taps = b->d_taps; a.n_out = c->n_out; a.ntaps = c->ntaps; a.down = c->down; a.d0 = c->d0;
+    a.TO = plan.TO; a.fir_phase = plan.fir_phase; a.tphase = b->d_tphase;
+    a.scale = (float)((double)c->sample_rate / (2.0 * M_PI * 75000.0));
+    a.bfo_c = 2.0 * M_PI * c->bfo_hz;   // Python: (2j*np.pi) * offset_hz
+    a.pll_alpha = c->pll_alpha; a.pll_beta = c->pll_beta;
     *out = b.release();
     return WH_OK;
 }
@@ -2105,11 +2346,8 @@ extern "C" void wh_chanbank_destroy(wh_chanbank *b) { delete b; }
 
 extern "C" size_t wh_chanbank_workspace_bytes(const wh_chanbank *b, size_t n_chunks) {
     if (!b) return 0;
-    size_t rows = n_chunks * (size_t)b->cfg.n_channels;
-    size_t bytes = rows * 2 * sizeof(double);
-    if (!b->fused) bytes += rows * (size_t)b->cfg.chunk_len * sizeof(float);
-    if (b->nr) bytes += rows * (size_t)b->nr_frames * NR_BINS * (sizeof(float2) + sizeof(float)) + rows * NR_BINS * 2 * sizeof(float);
-    return bytes;
+    const ChanWorkspace w = chanbank_workspace(b, n_chunks);
+    return (w.acc + w.S0) * sizeof(double) + (w.fm + w.araw + w.nr_mag + w.nr_sel) * sizeof(float) + w.nr_stft * sizeof(float2);
 }
 
 extern "C" int wh_chanbank_run(wh_chanbank *b, const void *d_in, size_t n_chunks, float *d_audio, float *d_metrics,
@@ -2125,199 +2363,23 @@ extern "C" int wh_chanbank_run_wire(wh_chanbank *b, const void *d_in, size_t n_c
     if (wire_format < 0 || wire_format > 2 || (wire_format != 0 && !d_wire))
         return set_err(WH_E_ARG, "wh_chanbank_run_wire: wire_format 0 (none) / 1 (int16 PCM) / 2 (clipped float32) with a buffer");
     if (n_chunks > 65535) return set_err(WH_E_ARG, "wh_chanbank_run: n_chunks > 65535 per call");
+    if (b->plan.nr && n_chunks * (size_t)b->cfg.n_channels > 65535)
+        return set_err(WH_E_ARG, "wh_chanbank_run: noise reduction supports <= 65535 rows per call");
     hipStream_t st = as_stream(stream);
-    const wh_chanbank_cfg &c = b->cfg;
-    const size_t rows = n_chunks * (size_t)c.n_channels;
-    const bool resample = c.ntaps > 0;
-    if (n_chunks > b->cap_chunks) {  // grow the workspace (synchronises; steady state never does)
-        DevBuf<double> acc, S0;
-        DevBuf<float> araw, fm, nr_mag, nr_sel;
-        DevBuf<float2> nr_stft;
-        WH_HIP(acc.alloc(rows * 2));
-        if (b->fused) WH_HIP(araw.alloc(n_chunks * (size_t)c.chunk_len));
-        if (!b->fused && (resample || b->nr)) WH_HIP(fm.alloc(rows * (size_t)c.chunk_len));
-        if (b->d_G) {
-            // (segments per row: the warm-up form's wave count is a property of the bank, see below)
-            int rw, rg;
-            rows_shape(c, true, &rw, &rg);
-            WH_HIP(S0.alloc(rows * (size_t)(64 * rw * rg) * b->start_ep));
-        }
-        if (b->nr) {
-            WH_HIP(nr_stft.alloc(rows * (size_t)b->nr_frames * NR_BINS));
-            WH_HIP(nr_mag.alloc(rows * (size_t)b->nr_frames * NR_BINS));
-            WH_HIP(nr_sel.alloc(rows * (size_t)NR_BINS * 2));
-        }
-        WH_HIP(sync_before_swap(st));
-        b->d_acc = std::move(acc); b->d_araw = std::move(araw); b->d_fm = std::move(fm); b->d_S0 = std::move(S0);
-        b->d_nr_stft = std::move(nr_stft); b->d_nr_mag = std::move(nr_mag); b->d_nr_sel = std::move(nr_sel);
-        b->cap_chunks = n_chunks;
-    }
-    WH_HIP(hipMemsetAsync(b->d_acc, 0, rows * 2 * sizeof(double), st));
-    FmArgs a;
+    int rc;
+    if ((rc = chanbank_reserve(b, n_chunks, st)) != WH_OK) return rc;
+    WH_HIP(hipMemsetAsync(b->d_acc, 0, n_chunks * b->cfg.n_channels * 2 * sizeof(double), st));
+    FmArgs a = b->args;
     a.in = d_in;
     a.audio = d_audio;
     a.acc = b->d_acc;
-    a.fm_out = (resample || b->nr) ? b->d_fm : d_audio;   // no resampling, no length change: rows are the audio
-    a.rows_src = nullptr;
-    a.skip_fm_sum = (!b->fused && (c.n_stages > 0 || c.agc)) ? 1 : 0;
-    a.nco_c = b->d_nco;
-    a.taps = b->d_taps;
-    a.fmt = c.input_format;
-    a.N = c.chunk_len;
-    a.K = c.n_channels;
-    a.n_out = c.n_out;
-    a.ntaps = c.ntaps;
-    a.down = c.down;
-    a.d0 = c.d0;
-    a.TO = b->TO;
-    a.fir_phase = b->fir_phase;
-    a.tphase = b->d_tphase;
-    a.araw = nullptr;
-    a.R = 1;
-    a.scale = (float)((double)c.sample_rate / (2.0 * M_PI * 75000.0));
-    a.demod = c.demod;
-    a.bfo_c = 2.0 * M_PI * c.bfo_hz;   // Python: (2j*np.pi) * offset_hz
-    a.fs_d = (double)c.sample_rate;
-    a.pll_alpha = c.pll_alpha;
-    a.pll_beta = c.pll_beta;
-    if (b->fused) {
-        // raw discriminator angles + sum |x|^2, once per chunk (shared by the channels)
-        {
-            const unsigned gx = (unsigned)((c.chunk_len + 4095) / 4096);
-            if (c.input_format == 1) hipLaunchKernelGGL(fm_rawdisc_kernel<1>, dim3(gx, (unsigned)n_chunks), dim3(256), 0, st, a, b->d_araw);
-            else hipLaunchKernelGGL(fm_rawdisc_kernel<0>, dim3(gx, (unsigned)n_chunks), dim3(256), 0, st, a, b->d_araw);
-            WH_LAUNCH_CHECK();
-            a.araw = b->d_araw;
-        }
-        const int tiles = (c.n_out + b->TO - 1) / b->TO;
-        const int R = run_tiles(tiles, rows);
-        a.R = R;
-        hipLaunchKernelGGL(fmbank_fused_kernel<false>, dim3((tiles + R - 1) / R, c.n_channels, (unsigned)n_chunks), dim3(256),
-                           b->smem, st, a);
-        WH_LAUNCH_CHECK();
-    } else {
-        int per_block = 4 * 63 * 16;
-        int blocks = (c.chunk_len + per_block - 1) / per_block;
-        if (c.demod >= 3)
-            hipLaunchKernelGGL(sam_front_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, a, (int)rows);
-        else
-            hipLaunchKernelGGL(chan_front_kernel, dim3(blocks, c.n_channels, (unsigned)n_chunks), dim3(256), 0, st, a);
-        WH_LAUNCH_CHECK();
-        if (c.n_stages > 0 || c.agc) {
-            AgcDev g;
-            g.on = c.agc;
-            g.target = c.agc_target;
-            g.max_gain = c.agc_max_gain;
-            g.att_b0 = c.agc_att_b0; g.att_a1 = c.agc_att_a1;
-            g.rel_b0 = c.agc_rel_b0; g.rel_a1 = c.agc_rel_a1;
-            // time-parallel mode when it at least halves the sequential depth (see chan_rows_kernel)
-            int seg = 0, rw = 1, rg = 1;
-            if (!c.agc && c.iir_warmup > 0 && c.n_stages > 0) {
-                const int sg = (c.chunk_len + 63) / 64;
-                if (sg + c.iir_warmup <= c.chunk_len / 2) {
-                    rows_shape(c, b->d_G != nullptr, &rw, &rg);
-                    seg = (c.chunk_len + 64 * rw * rg - 1) / (64 * rw * rg);
-                }
-            }
-            const double *S0 = nullptr;
-            if (seg && b->d_G) {   // start states of all segments, chip-wide (iir_start_kernel)
-                const dim3 sg2((unsigned)rows, (unsigned)((64 * rw * rg + START_SEGS - 1) / START_SEGS));
-#define WH_START(EP_)                                                                                                     \
-    hipLaunchKernelGGL(iir_start_kernel<EP_>, sg2, dim3(256), 0, st, a.fm_out, c.chunk_len, seg, c.iir_warmup, 64 * rw * rg, \
-                       b->d_G, b->d_S0)
-                switch (b->start_ep) {
-                    case 2: WH_START(2); break;
-                    case 4: WH_START(4); break;
-                    case 6: WH_START(6); break;
-                    case 8: WH_START(8); break;
-                    case 10: WH_START(10); break;
-                    case 12: WH_START(12); break;
-                    case 14: WH_START(14); break;
-                    default: WH_START(16); break;
-                }
-#undef WH_START
-                WH_LAUNCH_CHECK();
-                S0 = b->d_S0;
-            }
-            if (b->scan_seg) {
-                hipLaunchKernelGGL(chan_rows_scan_kernel, dim3((unsigned)rows), dim3(64 * b->scan_w),
-                                   (size_t)b->scan_w * ROWS_CH * 65 * sizeof(float), st, a.fm_out, b->d_acc, c.chunk_len,
-                                   b->stages, c.n_stages, g, b->scan_seg, b->d_pow);
-                WH_LAUNCH_CHECK();
-            } else {
-            const dim3 rgrid(seg ? (unsigned)rows : (unsigned)((rows + 63) / 64), (unsigned)(seg ? rg : 1));
-            const size_t tile_bytes = (size_t)rw * ROWS_CH * 65 * sizeof(float);
-#define WH_ROWS(NS_)                                                                                                      \
-    do {                                                                                                                  \
-        if (tile_bytes > 64 * 1024)                                                                                       \
-            WH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(chan_rows_kernel<NS_>),                             \
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_bytes));                     \
-        hipLaunchKernelGGL(chan_rows_kernel<NS_>, rgrid, dim3(64 * rw), tile_bytes, st, a.fm_out, b->d_acc, (int)rows,    \
-                           c.chunk_len, b->stages, g, seg, c.iir_warmup, S0, b->start_ep);                                \
-    } while (0)
-            switch (c.n_stages) {
-                case 0: WH_ROWS(0); break;
-                case 1: WH_ROWS(1); break;
-                case 2: WH_ROWS(2); break;
-                case 3: WH_ROWS(3); break;
-                case 4: WH_ROWS(4); break;
-                case 5: WH_ROWS(5); break;
-                case 6: WH_ROWS(6); break;
-                case 7: WH_ROWS(7); break;
-                default: WH_ROWS(8); break;
-            }
-#undef WH_ROWS
-            WH_LAUNCH_CHECK();
-            }
-        }
-        if (b->nr) {
-            const int F = b->nr_frames;
-            if (rows > 65535) return set_err(WH_E_ARG, "wh_chanbank_run: noise reduction supports <= 65535 rows per call");
-            hipLaunchKernelGGL(nr_stft_kernel, dim3(F, (unsigned)rows), dim3(256), 0, st, b->d_fm, c.chunk_len, F,
-                               b->d_nr_win, b->d_nr_tw, b->d_nr_stft, b->d_nr_mag);
-            WH_LAUNCH_CHECK();
-            const double virt = (double)(F - 1) * 0.1;   // np.percentile(..., 10), method 'linear'
-            int k_lo = (int)floor(virt);
-            int k_hi = k_lo + 1 < F ? k_lo + 1 : F - 1;
-            if (F <= RANK_MAX)
-                hipLaunchKernelGGL(rank_select_kernel, dim3((unsigned)((rows * NR_BINS + 3) / 4)), dim3(256),
-                                   (size_t)4 * F * sizeof(float), st, b->d_nr_mag, (int)(rows * NR_BINS), F, k_lo, k_hi, b->d_nr_sel);
-            else
-                hipLaunchKernelGGL(select_kth_kernel, dim3((unsigned)(rows * NR_BINS), 2), dim3(256), 0, st, b->d_nr_mag, F, k_lo,
-                                   k_hi, b->d_nr_sel);
-            WH_LAUNCH_CHECK();
-            WH_HIP(hipMemsetAsync(b->d_fm, 0, rows * (size_t)c.chunk_len * sizeof(float), st));
-            hipLaunchKernelGGL(nr_istft_kernel, dim3(F, (unsigned)rows), dim3(256), 0, st, b->d_fm, c.chunk_len, F,
-                               b->d_nr_win, b->d_nr_tw, b->d_nr_stft, b->d_nr_sel, k_lo, (float)(virt - (double)k_lo),
-                               c.nr_reduction_linear);
-            WH_LAUNCH_CHECK();
-            hipLaunchKernelGGL(nr_norm_kernel, dim3((unsigned)rows), dim3(256), 0, st, b->d_fm, c.chunk_len, F, b->d_nr_win,
-                               b->d_acc);
-            WH_LAUNCH_CHECK();
-        }
-        const size_t n_fm = b->nr ? (size_t)b->nr_len : (size_t)c.chunk_len;
-        if (resample && b->rows_fir) {
-            const int tiles = (c.n_out + b->TO - 1) / b->TO;
-            const int R = run_tiles(tiles, rows);
-            a.R = R;
-            a.rows_src = b->d_fm;
-            hipLaunchKernelGGL(fmbank_fused_kernel<true>, dim3((tiles + R - 1) / R, c.n_channels, (unsigned)n_chunks), dim3(256),
-                               b->smem, st, a);
-            WH_LAUNCH_CHECK();
-        } else if (resample) {
-            int rc = launch_resample(b->d_fm, n_fm, (size_t)c.chunk_len, rows, d_audio, (size_t)c.n_out, b->d_taps, c.ntaps,
-                                     c.up, c.down, c.d0, st);
-            if (rc != WH_OK) return rc;
-        } else if (b->nr) {   // compact the shortened rows into the audio buffer
-            WH_HIP(hipMemcpy2DAsync(d_audio, (size_t)c.n_out * sizeof(float), b->d_fm, (size_t)c.chunk_len * sizeof(float),
-                                    (size_t)c.n_out * sizeof(float), rows, hipMemcpyDeviceToDevice, st));
-        }
-    }
-    hipLaunchKernelGGL(fmbank_finalize_kernel, dim3((unsigned)rows), dim3(256), 0, st, d_audio, b->d_acc, d_metrics,
-                       c.chunk_len, b->nr ? b->nr_len : c.chunk_len, c.n_out, b->post, b->d_squelch, c.n_channels, wire_format,
-                       d_wire, b->fused ? 1 : 0);
-    WH_LAUNCH_CHECK();
-    return WH_OK;
+    a.fm_out = b->plan.out == Output::RowsAreAudio ? d_audio : b->d_fm.get();   // no resampling, no length change
+    if ((rc = launch_front(b, a, n_chunks, st)) != WH_OK) return rc;
+    if ((rc = launch_start_states(b, a.fm_out, n_chunks, st)) != WH_OK) return rc;
+    if ((rc = launch_rows(b, a.fm_out, n_chunks, st)) != WH_OK) return rc;
+    if ((rc = launch_nr(b, n_chunks, st)) != WH_OK) return rc;
+    if ((rc = launch_output(b, a, n_chunks, st)) != WH_OK) return rc;
+    return launch_finalize(b, d_audio, d_metrics, wire_format, d_wire, n_chunks, st);
 }
 
 /* Channel.update_signal_metrics (capture.py:749-798) for K channels of one chunk: h_out[k] =
@@ -2331,21 +2393,20 @@ extern "C" int wh_channel_signal_metrics(const void *d_in, int input_format, siz
     hipStream_t st = as_stream(stream);
     std::vector<float> nco(K);
     for (int k = 0; k < K; ++k) nco[k] = h_offsets_hz[k] == 0 ? 0.0f : nco_const(h_offsets_hz[k], sample_rate);
-    float *d_nco = nullptr, *d_rows = nullptr, *d_sel = nullptr, *d_rssi = nullptr;
-    double *d_acc = nullptr;
-    WH_HIP(hipMallocAsync(reinterpret_cast<void **>(&d_nco), K * sizeof(float), st));
-    WH_HIP(hipMallocAsync(reinterpret_cast<void **>(&d_rows), (size_t)K * n * sizeof(float), st));
-    WH_HIP(hipMallocAsync(reinterpret_cast<void **>(&d_sel), (size_t)K * 2 * sizeof(float), st));
-    WH_HIP(hipMallocAsync(reinterpret_cast<void **>(&d_rssi), (size_t)K * sizeof(float), st));
-    WH_HIP(hipMallocAsync(reinterpret_cast<void **>(&d_acc), (size_t)K * 2 * sizeof(double), st));
+    StreamBuf<float> d_nco, d_rows, d_sel, d_rssi;
+    StreamBuf<double> d_acc;
+    WH_HIP(d_nco.alloc(K, st));
+    WH_HIP(d_rows.alloc((size_t)K * n, st));
+    WH_HIP(d_sel.alloc((size_t)K * 2, st));
+    WH_HIP(d_rssi.alloc(K, st));
+    WH_HIP(d_acc.alloc((size_t)K * 2, st));
     WH_HIP(hipMemcpyAsync(d_nco, nco.data(), K * sizeof(float), hipMemcpyHostToDevice, st));
     WH_HIP(hipMemsetAsync(d_acc, 0, (size_t)K * 2 * sizeof(double), st));
-    FmArgs a;
-    a.in = d_in; a.audio = nullptr; a.acc = d_acc; a.fm_out = d_rows; a.rows_src = nullptr; a.skip_fm_sum = 0; a.nco_c = d_nco; a.taps = nullptr;
-    a.fmt = input_format; a.N = (int)n; a.K = K; a.n_out = 0; a.ntaps = 0; a.down = 1; a.d0 = 0; a.TO = 1; a.R = 1; a.fir_phase = 0; a.tphase = nullptr; a.araw = nullptr;
-    a.scale = 0.f; a.demod = 1; a.bfo_c = 0.0; a.fs_d = (double)sample_rate; a.pll_alpha = a.pll_beta = 0.0;
-    const int per_block = 4 * 63 * 16;
-    hipLaunchKernelGGL(chan_front_kernel, dim3((unsigned)((n + per_block - 1) / per_block), K, 1), dim3(256), 0, st, a);
+    FmArgs a = fm_args(input_format, (int)n, K, d_nco, 1, sample_rate);   // AM envelope
+    a.in = d_in;
+    a.acc = d_acc;
+    a.fm_out = d_rows;
+    hipLaunchKernelGGL(chan_front_kernel, dim3(chan_front_blocks(n), K, 1), dim3(256), 0, st, a);
     WH_LAUNCH_CHECK();
     const int k_lo = (int)(n / 10), k_hi = (int)(n - n / 10 - 1);
     hipLaunchKernelGGL(select_kth_kernel, dim3(K, 2), dim3(256), 0, st, d_rows, (int)n, k_lo, k_hi, d_sel);
@@ -2361,11 +2422,6 @@ extern "C" int wh_channel_signal_metrics(const void *d_in, int input_format, siz
         h_out[k * 3 + 1] = sel[k * 2];
         h_out[k * 3 + 2] = sel[k * 2 + 1];
     }
-    WH_HIP(hipFreeAsync(d_nco, st));
-    WH_HIP(hipFreeAsync(d_rows, st));
-    WH_HIP(hipFreeAsync(d_sel, st));
-    WH_HIP(hipFreeAsync(d_rssi, st));
-    WH_HIP(hipFreeAsync(d_acc, st));
     return WH_OK;
 }
 
@@ -2403,17 +2459,15 @@ extern "C" int wh_noise_blanker(const float *d_x, float *d_out, size_t n, float 
     if (!d_x || !d_out || d_x == d_out || n > ((size_t)1 << 24) || blanking_width < 0 || blanking_width > 4096)
         return set_err(WH_E_ARG, "wh_noise_blanker: bad arguments (out of place, n <= 2^24)");
     hipStream_t st = as_stream(stream);
-    float *d_mag = nullptr, *d_sel = nullptr;
-    WH_HIP(hipMallocAsync(reinterpret_cast<void **>(&d_mag), n * sizeof(float), st));
-    WH_HIP(hipMallocAsync(reinterpret_cast<void **>(&d_sel), 2 * sizeof(float), st));
+    StreamBuf<float> d_mag, d_sel;
+    WH_HIP(d_mag.alloc(n, st));
+    WH_HIP(d_sel.alloc(2, st));
     hipLaunchKernelGGL(nb_abs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_x, d_mag, n);
     const int k_hi = (int)(n / 2), k_lo = (n & 1) ? k_hi : k_hi - 1;
     hipLaunchKernelGGL(select_kth_kernel, dim3(1, 2), dim3(256), 0, st, d_mag, (int)n, k_lo, k_hi, d_sel);
     hipLaunchKernelGGL(nb_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_x, d_sel, threshold_factor,
                        (int)n, blanking_width, (int)(n & 1), d_out);
     hipError_t e = hipGetLastError();
-    (void)hipFreeAsync(d_mag, st);
-    (void)hipFreeAsync(d_sel, st);
     if (e != hipSuccess) return set_err(WH_E_HIP, "wh_noise_blanker: %s", hipGetErrorString(e));
     return WH_OK;
 }

@@ -261,13 +261,12 @@ extern "C" int wh_binstats_update(const float *d_power_db, size_t n_frames, int 
 extern "C" int wh_audio_stats(const float *d_x, size_t n, float *h_out, void *stream) {
     if (!d_x || !h_out || n == 0) return set_err(WH_E_ARG, "wh_audio_stats: bad arguments");
     hipStream_t st = as_stream(stream);
-    float *d_out = nullptr;
-    WH_HIP(hipMallocAsync(reinterpret_cast<void **>(&d_out), 3 * sizeof(float), st));
+    StreamBuf<float> d_out;
+    WH_HIP(d_out.alloc(3, st));
     hipLaunchKernelGGL(audio_stats_kernel, dim3(1), dim3(256), 0, st, d_x, n, d_out);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(h_out, d_out, 3 * sizeof(float), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    (void)hipFreeAsync(d_out, st);
     if (e != hipSuccess) return set_err(WH_E_HIP, hipGetErrorString(e));
     return WH_OK;
 }

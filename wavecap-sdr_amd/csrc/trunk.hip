@@ -435,12 +435,12 @@ extern "C" int wh_scan_measure(const float *d_iq, size_t n, int sample_rate, con
     std::vector<float> nco(n_off);
     for (int i = 0; i < n_off; ++i)
         nco[i] = h_offsets_hz[i] == 0 ? 0.0f : (float)(-2.0 * M_PI * ((double)h_offsets_hz[i] / (double)sample_rate));
-    double *d_taps = nullptr, *d_part = nullptr, *d_res = nullptr;
-    float *d_nco = nullptr;
-    WH_HIP(hipMallocAsync(reinterpret_cast<void **>(&d_taps), ntaps * sizeof(double), st));
-    WH_HIP(hipMallocAsync(reinterpret_cast<void **>(&d_nco), n_off * sizeof(float), st));
-    WH_HIP(hipMallocAsync(reinterpret_cast<void **>(&d_part), (size_t)n_off * blocks * 2 * sizeof(double), st));
-    WH_HIP(hipMallocAsync(reinterpret_cast<void **>(&d_res), (size_t)n_off * 2 * sizeof(double), st));
+    StreamBuf<double> d_taps, d_part, d_res, d_sym, d_best;
+    StreamBuf<float> d_nco;
+    WH_HIP(d_taps.alloc(ntaps, st));
+    WH_HIP(d_nco.alloc(n_off, st));
+    WH_HIP(d_part.alloc((size_t)n_off * blocks * 2, st));
+    WH_HIP(d_res.alloc((size_t)n_off * 2, st));
     WH_HIP(hipMemcpyAsync(d_taps, h_taps, ntaps * sizeof(double), hipMemcpyHostToDevice, st));
     WH_HIP(hipMemcpyAsync(d_nco, nco.data(), n_off * sizeof(float), hipMemcpyHostToDevice, st));
     ScanArgs a;
@@ -452,7 +452,6 @@ extern "C" int wh_scan_measure(const float *d_iq, size_t n, int sample_rate, con
     hipLaunchKernelGGL(scan_final_kernel, dim3((n_off + 63) / 64), dim3(64), 0, st, d_part, blocks, n_off, n_out, d_res);
     WH_LAUNCH_CHECK();
     WH_HIP(hipMemcpyAsync(h_out, d_res, (size_t)n_off * 2 * sizeof(double), hipMemcpyDeviceToHost, st));
-    double *d_sym = nullptr, *d_best = nullptr;
     if (h_sync_corr) {
         // cc_scanner.py:289-325: 10 samples/symbol, fm = angle(y[1:] conj y[:-1]), symbols at 5::10
         for (int i = 0; i < n_off; ++i) h_sync_corr[i] = 0.0;
@@ -462,8 +461,8 @@ extern "C" int wh_scan_measure(const float *d_iq, size_t n, int sample_rate, con
         const int n_sym = have < symbols_count ? have : symbols_count;
         const int search_len = n_sym - 24;           // min(len(symbol_samples) - 24, symbols_count - 24)
         if (n_out >= 10 * 24 + 10 && symbols_count >= 24 && search_len > 0) {
-            WH_HIP(hipMallocAsync(reinterpret_cast<void **>(&d_sym), (size_t)n_off * n_sym * sizeof(double), st));
-            WH_HIP(hipMallocAsync(reinterpret_cast<void **>(&d_best), (size_t)n_off * sizeof(double), st));
+            WH_HIP(d_sym.alloc((size_t)n_off * n_sym, st));
+            WH_HIP(d_best.alloc(n_off, st));
             hipLaunchKernelGGL(scan_symbols_kernel, dim3((n_sym + 255) / 256, n_off), dim3(256), ntaps * sizeof(double), st,
                                a, d_sym, n_sym);
             WH_LAUNCH_CHECK();
@@ -473,11 +472,5 @@ extern "C" int wh_scan_measure(const float *d_iq, size_t n, int sample_rate, con
         }
     }
     WH_HIP(hipStreamSynchronize(st));   // results are host scalars (the scanner picks a channel with them)
-    if (d_sym) WH_HIP(hipFreeAsync(d_sym, st));
-    if (d_best) WH_HIP(hipFreeAsync(d_best, st));
-    WH_HIP(hipFreeAsync(d_taps, st));
-    WH_HIP(hipFreeAsync(d_nco, st));
-    WH_HIP(hipFreeAsync(d_part, st));
-    WH_HIP(hipFreeAsync(d_res, st));
     return WH_OK;
 }

@@ -138,6 +138,38 @@ class DevBuf {
     size_t n_ = 0;
 };
 
+// Owning stream-ordered device buffer of n elements of T: move-only, allocated with hipMallocAsync on a stream and
+// released with hipFreeAsync on the same stream when the owner goes out of scope, an early return included.  Converts
+// to T * like DevBuf.
+template <class T>
+class StreamBuf {
+  public:
+    StreamBuf() = default;
+    StreamBuf(const StreamBuf &) = delete;
+    StreamBuf &operator=(const StreamBuf &) = delete;
+    StreamBuf(StreamBuf &&o) noexcept : p_(std::exchange(o.p_, nullptr)), st_(o.st_) {}
+    StreamBuf &operator=(StreamBuf &&o) noexcept { std::swap(p_, o.p_); std::swap(st_, o.st_); return *this; }   // the old buffer goes with o
+    ~StreamBuf() { release(); }
+
+    // replaces the contents with n uninitialised elements ordered on st; on failure the buffer is left empty
+    hipError_t alloc(size_t n, hipStream_t st) {
+        release();
+        hipError_t e = hipMallocAsync(reinterpret_cast<void **>(&p_), n * sizeof(T), st);
+        if (e != hipSuccess) p_ = nullptr;
+        else st_ = st;
+        return e;
+    }
+    operator T *() const { return p_; }
+
+  private:
+    void release() {
+        if (p_) (void)hipFreeAsync(p_, st_);
+        p_ = nullptr;
+    }
+    T *p_ = nullptr;
+    hipStream_t st_ = nullptr;
+};
+
 // Owning HIP stream or event: move-only, created with flags, released on destruction.  Converts to the raw handle.
 template <class H, hipError_t (*Create)(H *, unsigned), hipError_t (*Destroy)(H)>
 class HipHandle {
